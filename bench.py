@@ -1,7 +1,7 @@
 #!/usr/bin/env python
 """Headline benchmark: Mpixels/s of displacement-field extraction on MI355X.
 
-    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--dtype f32|f64]
+    python bench.py [--gpus N] [--steps K] [--warmup W] [--size S] [--dtype f32|f64] [--full] [--dump-outputs DIR]
 
 N = 1 (BASELINE.json configs[2]): 4096 x 4096 synthetic hex moire, 3 Bragg peaks x 16 reference
 k-vectors (explicit 4x4 lists), sigma = 10, weighted DCT-PCG unwrap with kmax = 10, fp32.  One step =
@@ -9,16 +9,27 @@ one whole extract_displacement_field call through the C ABI of libgpa_hip.so on 
 resident in HBM (mean, 48 lock-ins, select, phases/weights, per-pixel least squares, two unwraps)
 PLUS the download of u to page-locked host memory ("D2H of u included"), which runs on
 the plan's copy stream while the kernels of the next step execute.  The PCG of the timed step stops by the
-reference's test alone (kmax or ||r|| < 1e-9 ||r0||: 10 + 10 iterations on this image) -- the library default; the
-opt-in f32 residual floor (F32_EPS_FLOOR=4e-6) is the extra key `early_stop`.  Other extra keys: `resident_only`
-(the same loop with u left in HBM), `f64` (the reference's own precision), `host_call` (host arrays in and out: H2D
-and D2H inside the call), `kernels` (per-kernel HIP-event times with the roofline that bounds each), `cpu_baseline`.
+reference's test alone (kmax or ||r|| < 1e-9 ||r0||: 10 + 10 iterations on this image) -- the library default.
+
+A plain run sets up, warms up, times the K steps and prints the line (`value`, `ms_per_step` of the headline and the
+configuration); nothing else.  --full adds every other leg after the headline: `early_stop` (the opt-in f32 residual
+floor F32_EPS_FLOOR=4e-6), `resident_only` (the same loop with u left in HBM), `kernels` (per-kernel HIP-event times
+with the roofline that bounds each), `f64` (the reference's own precision), `config2`, `small_image_stacks`,
+`host_call` (host arrays in and out: H2D and D2H inside the call), `config5_single_gpu`, `pipeline_end_to_end`,
+`cpu_baseline`; the --no-* switches skip single legs of a --full run.
+
+--dump-outputs DIR: after the timed steps, the field u (2, N, M) of the LAST timed step -- what a caller of the timed
+path receives -- goes to DIR/u.npy in the plan's precision; a u larger than DUMP_BUDGET_BYTES is replaced by a fixed,
+seeded sample of its pixels (DIR/u_sample.npy, (2, m), and the flat pixel indices DIR/u_sample_index.npy).  The inputs
+are the same in every run with the same arguments, so two builds can be compared output for output.
 
 N > 1 (one rank per GPU; `--gpus N` without a launcher starts N fresh child processes through
 torch.distributed.run before this process touches a GPU): the tile pipeline of BASELINE configs[3-4],
 pygpa_amd.distributed.TiledPipeline, on an image of N x 4096^2 pixels (N = 4: 8192^2 = configs[3]):
 halo windows dealt over the ranks -> all_gather of the gradient tiles -> global unwrap -> broadcast of u.
-Weak scaling: pixels per GPU are fixed.
+Weak scaling: pixels per GPU are fixed.  --full adds the diagnostics after the timed region (per-rank device stage
+times, the tile-sharded Lawler-Fujita, the roofline of the tile stage); --dump-outputs writes the u of the last image
+from the rank that holds it.
 
 Rank 0 prints ONE JSON line.
 """
@@ -44,7 +55,7 @@ def parse_args():
     ap = argparse.ArgumentParser()
     ap.add_argument('--gpus', type=int, default=1)
     # (defaults: the timed loop ends with the pipeline's drain -- the last image's D2H of u, 2.6 ms, overlaps nothing -- which
-    #  100 steps amortise to 0.5 % of a step where 20 steps left 2.4 %: tools/ab_steps.sh; the whole default run stays under a minute)
+    #  100 steps amortise to 0.5 % of a step where 20 steps left 2.4 %: tools/ab_steps.sh; a plain run takes seconds, --full minutes)
     ap.add_argument('--steps', type=int, default=100)
     ap.add_argument('--warmup', type=int, default=5)
     ap.add_argument('--size', type=int, default=4096)
@@ -55,6 +66,10 @@ def parse_args():
     ap.add_argument('--inflight', type=int, default=1,
                     help='N = 1: images in flight (one plan each; 1 = strictly one after the other). Small images leave most '
                          'of the GPU idle between their ~45 dependent kernels; several in flight fill it')
+    ap.add_argument('--full', action='store_true',
+                    help='besides the headline, run every other leg and diagnostic (the --no-* switches skip single legs)')
+    ap.add_argument('--dump-outputs', metavar='DIR', default=None,
+                    help='write the u of the last timed step to DIR/*.npy (a seeded sample of it above %d MB)' % (DUMP_BUDGET_BYTES // 10**6))
     ap.add_argument('--no-cpu', action='store_true', help='skip the CPU baseline leg')
     ap.add_argument('--no-f64', action='store_true', help='skip the f64 leg')
     ap.add_argument('--no-lf', action='store_true', help='N > 1: skip the tile-sharded Lawler-Fujita diagnostic after the timed region')
@@ -66,7 +81,38 @@ def parse_args():
     ap.add_argument('--share-device', action='store_true', help='N > 1: every rank uses GPU 0 (test aid, with --backend gloo)')
     ap.add_argument('--schedule', default='stream', choices=['stream', 'step'],
                     help='N > 1: image-pipelined schedule (TiledPipeline.run_stream) or the unpipelined step()')
-    return ap.parse_args()
+    args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error('--steps must be >= 1 and --warmup >= 0')
+    return args
+
+
+# -------------------------------------------------------------------------------------------------
+# --dump-outputs
+# -------------------------------------------------------------------------------------------------
+DUMP_BUDGET_BYTES = 64 * 10**6     # all files of one --dump-outputs together
+DUMP_SAMPLE_PIXELS = 1 << 21       # pixels kept of a field above the budget (f64: 2 x 2^21 x 8 B + the indices = 50 MB)
+DUMP_SAMPLE_SEED = 20240601
+
+
+def dump_outputs(path, name, field):
+    """Write `field` (C, N, M) as path/<name>.npy, float32 or float64 as computed.  Above DUMP_BUDGET_BYTES it writes a
+    fixed, seeded sample of DUMP_SAMPLE_PIXELS pixel positions instead -- the same positions for every build and run of a
+    shape: path/<name>_sample.npy (C, m) and the flat pixel indices as path/<name>_sample_index.npy (float64, exact).
+    Returns the names of the files written."""
+    field = np.asarray(field)
+    if field.dtype not in (np.float32, np.float64):
+        raise TypeError('dump_outputs: %s is %s, not float32 / float64' % (name, field.dtype))
+    os.makedirs(path, exist_ok=True)
+    if field.nbytes <= DUMP_BUDGET_BYTES:
+        np.save(os.path.join(path, name + '.npy'), np.ascontiguousarray(field))
+        return [name + '.npy']
+    flat = field.reshape(field.shape[0], -1)
+    m = min(DUMP_SAMPLE_PIXELS, flat.shape[1])
+    idx = np.sort(np.random.default_rng(DUMP_SAMPLE_SEED).choice(flat.shape[1], m, replace=False))
+    np.save(os.path.join(path, name + '_sample.npy'), np.ascontiguousarray(flat[:, idx]))
+    np.save(os.path.join(path, name + '_sample_index.npy'), idx.astype(np.float64))
+    return [name + '_sample.npy', name + '_sample_index.npy']
 
 
 # -------------------------------------------------------------------------------------------------
@@ -204,6 +250,13 @@ class SingleGPU:
         self.run(steps, download)
         return time.perf_counter() - t0
 
+    def last_u(self, nsteps):
+        """the host copy of u that step nsteps - 1 of the last run(nsteps, download=True) landed in"""
+        i = nsteps - 1
+        pl, j = i % self.depth, (i // self.depth) & 1
+        self.plans[pl].download_wait(j)
+        return np.array(self.h_u[pl][j])
+
     def profile(self, reps=3):
         self.plan.set_profiling(True)
         stage = np.zeros(5)
@@ -254,9 +307,10 @@ def load_counters(name='counters.json'):
     return c
 
 
-def measure(n, knx, kny, np_dt, kmax, steps, warmup, depth=1, profile=True):
-    """One configuration on GPU 0: timed loop with the D2H of u, the same loop with u left in HBM, and (profile) the
-    per-kernel HIP-event table with the roofline of the dominant kernel."""
+def measure(n, knx, kny, np_dt, kmax, steps, warmup, depth=1, profile=True, extras=True, dump_dir=None):
+    """One configuration on GPU 0: timed loop with the D2H of u (dump_dir: its last u written there) and, with `extras`,
+    the same loop with u left in HBM, (profile) the per-kernel HIP-event table with the roofline of the dominant kernel
+    and (f32) the early_stop loop."""
     from pygpa_amd.synthetic import hex_kvecs, explicit_klists
     P, K = 3, knx * kny
     kvecs = hex_kvecs(0.1, 7.0)
@@ -272,11 +326,15 @@ def measure(n, knx, kny, np_dt, kmax, steps, warmup, depth=1, profile=True):
     # ends the benchmark image's solves after 9 + 8 iterations instead of 10 + 10; it is reported as `early_stop`.
     dt = g.timed(steps, warmup, download=True)
     iters = g.plan.last_iters()
-    dt_res = g.timed(steps, 1, download=False)
     res = {'n': n, 'P': P, 'K': K, 'Bx': int(Bx), 'sigma': sigma, 'kvecs': kvecs, 'klists': klists, 'iters': list(iters),
-           'value': round(n * n * steps / dt / 1e6, 2), 'ms_per_step': round(dt / steps * 1e3, 4),
-           'resident_value': round(n * n * steps / dt_res / 1e6, 2), 'resident_ms': round(dt_res / steps * 1e3, 4),
-           'depth': g.depth}
+           'value': round(n * n * steps / dt / 1e6, 2), 'ms_per_step': round(dt / steps * 1e3, 4), 'depth': g.depth}
+    if dump_dir is not None:
+        dump_outputs(dump_dir, 'u', g.last_u(steps))
+    if not extras:
+        g.close()
+        return res
+    dt_res = g.timed(steps, 1, download=False)
+    res.update({'resident_value': round(n * n * steps / dt_res / 1e6, 2), 'resident_ms': round(dt_res / steps * 1e3, 4)})
     if profile:
         stage, kern = g.profile()
         L0, L1 = g.plan.fft_len(0), g.plan.fft_len(1)
@@ -423,7 +481,8 @@ def single_gpu(args):
     if args.only_pipeline:
         print(json.dumps({'pipeline_end_to_end': pipeline_end_to_end(n, knx, kny, np_dt, args.kmax)}), flush=True)
         return
-    m = measure(n, knx, kny, np_dt, args.kmax, args.steps, args.warmup, depth=args.inflight)
+    m = measure(n, knx, kny, np_dt, args.kmax, args.steps, args.warmup, depth=args.inflight, extras=args.full,
+                dump_dir=args.dump_outputs)
     P, K, sigma, kvecs, klists = m['P'], m['K'], m['sigma'], m['kvecs'], m['klists']
     out = {
         'metric': 'Mpixels/s displacement-field extraction (3 peaks, 4096^2 img) + achieved HBM GB/s',
@@ -440,9 +499,12 @@ def single_gpu(args):
                    'unwrap_iters': m['iters'], 'stopping_test': "the reference's alone (kmax or ||r|| < 1e-9 ||r0||); the library's f32 residual floor is off",
                    'd2h_of_u': 'included, overlapped with the next step (copy stream)',
                    'images_in_flight': m['depth']},
-        'resident_only': {'value': m['resident_value'], 'ms_per_step': m['resident_ms'],
-                          'note': 'same loop with u left in HBM (round-1 definition)'},
     }
+    if not args.full:
+        print(json.dumps(out), flush=True)
+        return
+    out['resident_only'] = {'value': m['resident_value'], 'ms_per_step': m['resident_ms'],
+                            'note': 'same loop with u left in HBM (round-1 definition)'}
     for key in ('early_stop', 'kernels', 'stage_ms', 'roofline', 'roofline_unwrap', 'whole_step'):
         if key in m:
             out[key] = m[key]
@@ -897,17 +959,27 @@ def multi_gpu(args, world, rank, local_rank):
         t = t.to(dev)
     dist.all_reduce(t, op=dist.ReduceOp.MAX)
     dt = float(t.item())
+    if args.dump_outputs is not None:
+        # the u of the last timed image, read after the timed region: run_stream leaves image i in its result buffer i & 1
+        # on rank owners(i)[0] (both components: the other owner has handed component 1 over); step() broadcasts u to every rank
+        last = args.steps - 1
+        if stream and rank == pipe.owners(last)[0]:
+            dump_outputs(args.dump_outputs, 'u', pipe._pu[last & 1].cpu().numpy())
+        elif not stream and rank == 0:
+            dump_outputs(args.dump_outputs, 'u', np.stack([c.cpu().numpy() for c in pipe.u]))
     # ---- diagnostics for the scaling line (after the timed region): what the backend says the world is, and per-rank
     #      stage times -- host times of the timed stream (enqueueing + waits) and DEVICE-inclusive times of one unpipelined
     #      step with the device drained after every stage
     #      (the timed value is complete at this point: a diagnostic that fails on every rank alike is reported, not fatal)
+    #      (--full only; a plain run reports the stream's host times)
     dev_ms, diag_err = {}, None
-    try:
-        pipe.step(timings=dev_ms)
-    except Exception as e:
-        diag_err = 'step(timings): %s: %s' % (type(e).__name__, e)
+    if args.full:
+        try:
+            pipe.step(timings=dev_ms)
+        except Exception as e:
+            diag_err = 'step(timings): %s: %s' % (type(e).__name__, e)
     lf_ms = None
-    if not args.no_lf and diag_err is None:
+    if args.full and not args.no_lf and diag_err is None:
         try:
             torch.cuda.synchronize(dev)
             t_lf = time.perf_counter()
@@ -917,9 +989,10 @@ def multi_gpu(args, world, rank, local_rank):
             lf_ms = (time.perf_counter() - t_lf) * 1e3
         except Exception as e:
             diag_err = 'undistort: %s: %s' % (type(e).__name__, e)
-    mine = {'rank': rank, 'tiles': len(pipe.mine), 'stream_host_ms_per_image': {k: round(v / max(args.steps, 1) * 1e3, 3) for k, v in pipe.stage_s.items()} if stream else None,
-            'step_device_ms': {k: round(v, 3) for k, v in dev_ms.items()}, 'undistort_tile_sharded_ms': None if lf_ms is None else round(lf_ms, 2),
-            'diagnostic_error': diag_err}
+    mine = {'rank': rank, 'tiles': len(pipe.mine), 'stream_host_ms_per_image': {k: round(v / max(args.steps, 1) * 1e3, 3) for k, v in pipe.stage_s.items()} if stream else None}
+    if args.full:
+        mine.update({'step_device_ms': {k: round(v, 3) for k, v in dev_ms.items()},
+                     'undistort_tile_sharded_ms': None if lf_ms is None else round(lf_ms, 2), 'diagnostic_error': diag_err})
     per_rank = [None] * world
     dist.all_gather_object(per_rank, mine)
     if rank == 0:
@@ -962,23 +1035,24 @@ def multi_gpu(args, world, rank, local_rank):
             'ranks': {'world_size_reported_by_backend': dist.get_world_size(), 'backend': dist.get_backend(),
                       'rccl_version': list(torch.cuda.nccl.version()) if args.backend == 'nccl' else None,
                       'devices_visible': torch.cuda.device_count(), 'per_rank': per_rank,
-                      'note': 'stream_host_ms = host time of the timed image stream per stage (enqueueing and waits); step_device_ms = one '
+                      'note': 'stream_host_ms = host time of the timed image stream per stage (enqueueing and waits); with --full only: step_device_ms = one '
                               'unpipelined step() after the timed region with the device drained after every stage; '
                               'undistort_tile_sharded_ms = TiledPipeline.undistort (Lawler-Fujita of the stitched field, every rank its own '
                               'tiles, one all_reduce), first call, after the timed region -- NOT part of `value`'},
         }
         # roofline of the tile stage's dominant kernel (pass B on one window), measured on this rank AFTER the timed
-        # region on a whole-image call of the window's shape: the same kernel instantiation on the same rows
-        try:
-            torch.cuda.synchronize(dev)
-            m = measure(W, knx, kny, np_dt, args.kmax, 5, 1, profile=True)
-            rf = dict(m['roofline'])
-            rf['note'] = ('dominant kernel of the tile stage, from a %d^2 whole-image call on rank 0 after the timed region '
-                          '(same kernel, same window shape); ' % W) + str(rf.get('note', ''))
-            out['roofline'] = rf
-        except Exception as e:   # the scaling line must not die of its diagnostics
-            out['roofline'] = None
-            out['roofline_error'] = '%s: %s' % (type(e).__name__, e)
+        # region on a whole-image call of the window's shape: the same kernel instantiation on the same rows (--full)
+        if args.full:
+            try:
+                torch.cuda.synchronize(dev)
+                m = measure(W, knx, kny, np_dt, args.kmax, 5, 1, profile=True)
+                rf = dict(m['roofline'])
+                rf['note'] = ('dominant kernel of the tile stage, from a %d^2 whole-image call on rank 0 after the timed region '
+                              '(same kernel, same window shape); ' % W) + str(rf.get('note', ''))
+                out['roofline'] = rf
+            except Exception as e:   # the scaling line must not die of its diagnostics
+                out['roofline'] = None
+                out['roofline_error'] = '%s: %s' % (type(e).__name__, e)
         print(json.dumps(out), flush=True)
     pipe.close()
     dist.barrier()

@@ -69,3 +69,23 @@ def test_counters_are_refused_on_other_kernel_sources(tmp_path, monkeypatch):
     f.write_text(json.dumps({'_meta': {'commit': 'abc', 'csrc_sha256': 'somethingelse'}, 'passB_shared_kernel': {'hbm_bytes': 1}}))
     c = bench.load_counters()
     assert list(c) == ['_stale'] and 'not used' in c['_stale']
+
+
+def test_dump_outputs_whole_field_or_seeded_sample(tmp_path):
+    """--dump-outputs: a field within the budget is written whole; a larger one as the same seeded sample of pixel
+    positions in every run, with its indices, and the files of one dump stay within the budget"""
+    import bench
+    small = np.arange(2 * 64 * 48, dtype=np.float32).reshape(2, 64, 48)
+    assert bench.dump_outputs(str(tmp_path / 's'), 'u', small) == ['u.npy']
+    back = np.load(tmp_path / 's' / 'u.npy')
+    assert back.dtype == np.float32 and np.array_equal(back, small)
+    big = np.random.default_rng(3).standard_normal((2, 4096, 4096))        # float64, 268 MB
+    for run in ('a', 'b'):
+        files = bench.dump_outputs(str(tmp_path / run), 'u', big)
+        assert files == ['u_sample.npy', 'u_sample_index.npy']
+        assert sum(os.path.getsize(tmp_path / run / f) for f in files) <= bench.DUMP_BUDGET_BYTES
+    sa, ia = np.load(tmp_path / 'a' / 'u_sample.npy'), np.load(tmp_path / 'a' / 'u_sample_index.npy')
+    assert sa.dtype == np.float64 and ia.dtype == np.float64
+    assert np.array_equal(sa, np.load(tmp_path / 'b' / 'u_sample.npy')) and np.array_equal(ia, np.load(tmp_path / 'b' / 'u_sample_index.npy'))
+    assert np.array_equal(sa, big.reshape(2, -1)[:, ia.astype(np.int64)])
+    assert len(np.unique(ia)) == len(ia) == bench.DUMP_SAMPLE_PIXELS

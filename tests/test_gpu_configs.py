@@ -621,7 +621,7 @@ def test_bench_gpus_flag_spawns_ranks():
     """`python bench.py --gpus 2` (no launcher) must start 2 ranks itself and report n_gpus = 2 with the tile
     pipeline as the workload; here both ranks share GPU 0 over gloo and the image is small"""
     cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '2', '--warmup', '1', '--size', '256',
-           '--window', '128', '--kside', '2', '--backend', 'gloo', '--share-device']
+           '--window', '128', '--kside', '2', '--backend', 'gloo', '--share-device', '--full']
     env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
     r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
     assert r.returncode == 0, r.stderr.decode()[-2000:]
@@ -638,3 +638,64 @@ def test_bench_gpus_flag_spawns_ranks():
     assert r.returncode == 0, r.stderr.decode()[-2000:]
     out = json.loads([ln for ln in r.stdout.decode().splitlines() if ln.startswith('{')][0])
     assert out['config']['schedule'] == 'step' and 'all_gather' in out['config']['collectives']
+
+
+def test_bench_plain_run_times_the_steps_and_dumps_u(tmp_path):
+    """a plain `bench.py` run prints the headline line alone (no leg of --full) with `value` and `ms_per_step` of one and
+    the same timing, and `--dump-outputs` writes u: the field the library computes for the benchmark's image.  (Every step
+    computes that same image, so this does not tell the last step's buffer from an earlier one's.)"""
+    n, steps = 256, 3
+    d = tmp_path / 'out'
+    cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--steps', str(steps), '--warmup', '1', '--size', str(n),
+           '--dump-outputs', str(d)]
+    r = subprocess.run(cmd, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=600)
+    assert r.returncode == 0, r.stderr.decode()[-2000:]
+    lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith('{')]
+    assert len(lines) == 1
+    out = json.loads(lines[0])
+    for key in ('metric', 'value', 'unit', 'higher_is_better', 'dtype', 'ms_per_step'):
+        assert key in out, key
+    assert out['steps'] == steps and out['dtype'] == 'f32' and out['unit'] == 'Mpixels/s' and out['higher_is_better'] is True
+    assert abs(out['value'] - n * n / (out['ms_per_step'] * 1e-3) / 1e6) <= 0.01 * out['value']
+    for key in ('resident_only', 'kernels', 'roofline', 'f64', 'host_call', 'cpu_baseline', 'pipeline_end_to_end'):
+        assert key not in out, key
+    assert sorted(os.listdir(d)) == ['u.npy']
+    u = np.load(d / 'u.npy')
+    assert u.dtype == np.float32 and u.shape == (2, n, n) and np.isfinite(u).all()
+    kvecs = hex_kvecs(0.1, 7.0)
+    sigma = int(np.ceil(1 / np.linalg.norm(kvecs, axis=1).min()))
+    klists = np.stack(explicit_klists(kvecs, np.linalg.norm(kvecs, axis=1).mean() / 2.5, 4, 4))
+    img = hex_moire((n, n), kvecs, gaussian_bump_displacement((n, n)), noise=0.1, seed=100, dtype=np.float32)
+    plan = _lib.Plan((n, n), 48, np.float32, device=0)
+    try:
+        ref = plan.extract_displacement_field(img, kvecs, klists, sigma, 2 * sigma, kmax=10)[0]
+    finally:
+        plan.close()
+    assert np.abs(u - ref).max() <= 1e-5 * np.abs(ref).max()
+
+
+def test_bench_plain_multi_rank_run_dumps_u(tmp_path):
+    """a plain `bench.py --gpus 2` run (both ranks on GPU 0 over gloo) times the stream and nothing after it, and
+    `--dump-outputs` writes the u of the last image from the rank that holds it: the image-pipelined schedule and the
+    unpipelined step() dump the same field, bit for bit"""
+    env = {k: v for k, v in os.environ.items() if k not in ('RANK', 'WORLD_SIZE', 'LOCAL_RANK', 'MASTER_PORT')}
+    fields = {}
+    for sched in ('stream', 'step'):
+        d = tmp_path / sched
+        cmd = [sys.executable, os.path.join(ROOT, 'bench.py'), '--gpus', '2', '--steps', '3', '--warmup', '1', '--size', '256',
+               '--window', '128', '--kside', '2', '--backend', 'gloo', '--share-device', '--schedule', sched,
+               '--dump-outputs', str(d)]
+        r = subprocess.run(cmd, env=env, stdout=subprocess.PIPE, stderr=subprocess.PIPE, timeout=900)
+        assert r.returncode == 0, r.stderr.decode()[-2000:]
+        lines = [ln for ln in r.stdout.decode().splitlines() if ln.startswith('{')]
+        assert len(lines) == 1
+        out = json.loads(lines[0])
+        assert out['n_gpus'] == 2 and out['steps'] == 3 and out['value'] > 0 and out['config']['schedule'] == sched
+        assert 'roofline' not in out
+        for pr in out['ranks']['per_rank']:
+            assert 'step_device_ms' not in pr and 'undistort_tile_sharded_ms' not in pr
+        assert sorted(os.listdir(d)) == ['u.npy']
+        u = np.load(d / 'u.npy')
+        assert u.dtype == np.float32 and u.shape == (2, 512, 256) and np.isfinite(u).all() and np.abs(u).max() > 0
+        fields[sched] = u
+    assert np.array_equal(fields['stream'], fields['step'])

@@ -5,7 +5,7 @@
 ulimit -c 0
 cd "$GRAFT_REPO_ROOT" || exit 1
 one() {
-  env $1 timeout 300 python3 bench.py --no-cpu --no-f64 $ARGS 2>/dev/null | TAG="$1" python3 -c "
+  env $1 timeout 300 python3 bench.py --full --no-cpu --no-f64 $ARGS 2>/dev/null | TAG="$1" python3 -c "
 import json,sys,os
 d=json.loads(sys.stdin.read().strip().splitlines()[-1]); k=d['kernels']
 print('%-28s value %7.1f  resident %7.1f  early %7.1f |' % (os.environ['TAG'] or '(default)', d['value'], d['resident_only']['value'], d.get('early_stop', {}).get('value', 0)),

@@ -19,7 +19,7 @@ cd /tmp && export TMPDIR=/tmp
 export GPA_SERIAL_UNWRAP=1
 kstats() {   # tag, bench args...
   tag=$1; shift
-  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/ks_$tag -- python3 $ROOT/bench.py --steps 5 --warmup 1 --no-cpu --no-f64 "$@" > $out/ks_$tag.log 2>&1
+  timeout 600 rocprofv3 --kernel-trace --stats --output-format csv -d $out/ks_$tag -- python3 $ROOT/bench.py --full --steps 5 --warmup 1 --no-cpu --no-f64 "$@" > $out/ks_$tag.log 2>&1
   f=$(ls $out/ks_$tag/*/*kernel_stats.csv 2>/dev/null | head -1)
   [ -n "$f" ] && cp $f $out/kernel_stats_$tag.csv && head -12 $out/kernel_stats_$tag.csv | cut -c1-150
   rm -rf $out/ks_$tag
@@ -48,13 +48,13 @@ cd $ROOT && timeout 600 bash tools/gpu_unwrap_sizes.sh > /dev/null 2>&1; cp gpur
 SIZES="256 500 512 1000 1024 1500 2000 2048 3000 4096 8192 16384" timeout 900 bash tools/gpu_sizes.sh > /dev/null 2>&1; cp gpurun_out/sizes.txt $out/ 2>/dev/null
 cd /tmp
 bench_line() {   # the bench line LAST: its roofline reads the counters of this very tree (profiles/counters.json, checked by hash)
-  cd $ROOT; timeout 900 python bench.py > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"; tail -2 $out/bench.err; head -c 700 $out/bench.json; echo
+  cd $ROOT; timeout 900 python bench.py --full > $out/bench.json 2> $out/bench.err; echo "bench rc=$?"; tail -2 $out/bench.err; head -c 700 $out/bench.json; echo
 }
 if [ -n "$SKIP_PMC" ]; then bench_line; exit 0; fi
 i=0
 for set in "FETCH_SIZE" "WRITE_SIZE" "SQ_INSTS_VALU SQ_WAVES SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_WAVE_CYCLES SQ_WAIT_INST_ANY SQ_BUSY_CYCLES" \
            "SQ_WAIT_ANY SQ_ACTIVE_INST_ANY SQ_ACTIVE_INST_VALU SQ_INSTS_VALU_MFMA_F32 SQ_INSTS_VMEM_WR SQ_INSTS_VMEM_RD" "TCC_HIT_sum TCC_MISS_sum GRBM_GUI_ACTIVE"; do
-  timeout 300 rocprofv3 --pmc $set --output-format csv -d $out/pmc_$i -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu --no-f64 > $out/pmc_$i.log 2>&1
+  timeout 300 rocprofv3 --pmc $set --output-format csv -d $out/pmc_$i -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu --no-f64 > $out/pmc_$i.log 2>&1
   echo "pmc pass $i ($set): rc=$?"
   i=$((i+1))
 done
@@ -72,7 +72,7 @@ rm -rf $out/pmclf_[0-9]
 # f64 traffic of the sweep (18.2 GB moved for 4 GB needed)
 j=0
 for set in "FETCH_SIZE" "WRITE_SIZE"; do
-  timeout 300 rocprofv3 --pmc $set --output-format csv -d $out/pmc64_$j -- python3 $ROOT/bench.py --dtype f64 --steps 2 --warmup 1 --no-cpu --no-f64 > $out/pmc64_$j.log 2>&1
+  timeout 300 rocprofv3 --pmc $set --output-format csv -d $out/pmc64_$j -- python3 $ROOT/bench.py --full --dtype f64 --steps 2 --warmup 1 --no-cpu --no-f64 > $out/pmc64_$j.log 2>&1
   j=$((j+1))
 done
 COMMIT=${COMMIT:-unknown} PMC_DTYPE=f64 python3 tools/make_counters.py $out/counters_f64.json $out/pmc64_[0-9] > /dev/null

@@ -1,7 +1,7 @@
 ulimit -c 0
 ROOT=$GRAFT_REPO_ROOT; out=$ROOT/gpurun_out/salu; mkdir -p $out
 cd /tmp && export TMPDIR=/tmp
-timeout 300 rocprofv3 --pmc SQ_INSTS_SALU SQ_INSTS_VALU SQ_INSTS_SMEM SQ_WAVES SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d $out/p -- python3 $ROOT/bench.py --steps 2 --warmup 1 --no-cpu --no-f64 --no-config5 > $out/p.log 2>&1
+timeout 300 rocprofv3 --pmc SQ_INSTS_SALU SQ_INSTS_VALU SQ_INSTS_SMEM SQ_WAVES SQ_INSTS_LDS SQ_INSTS_VMEM_RD SQ_INSTS_VMEM_WR --output-format csv -d $out/p -- python3 $ROOT/bench.py --full --steps 2 --warmup 1 --no-cpu --no-f64 --no-config5 > $out/p.log 2>&1
 echo rc=$?
 python3 - <<PY
 import csv, glob, collections, re

@@ -17,8 +17,8 @@ run() {   # tag, program args...
 }
 for w in ${WHAT:-bench4096 unwrap8192 unwrap16384 tiles16384}; do
   case $w in
-    bench4096) GPA_SERIAL_UNWRAP=1 run 4096_f32 $ROOT/bench.py --steps 5 --warmup 1 --no-cpu --no-f64 ;;
-    bench4096f64) GPA_SERIAL_UNWRAP=1 run 4096_f64 $ROOT/bench.py --steps 5 --warmup 1 --no-cpu --no-f64 --dtype f64 ;;
+    bench4096) GPA_SERIAL_UNWRAP=1 run 4096_f32 $ROOT/bench.py --full --steps 5 --warmup 1 --no-cpu --no-f64 ;;
+    bench4096f64) GPA_SERIAL_UNWRAP=1 run 4096_f64 $ROOT/bench.py --full --steps 5 --warmup 1 --no-cpu --no-f64 --dtype f64 ;;
     unwrap*) n=${w#unwrap}; run unwrap_$n $ROOT/tools/unwrap_sizes.py --sizes $n --modes default --reps 2 ;;
     tiles*) n=${w#tiles}; run tiles_$n $ROOT/tools/stage_times.py --sizes $n ;;
     lf*) n=${w#lf}; run lf_$n $ROOT/tools/lf_times.py --sizes $n --reps 2 ;;

@@ -4,7 +4,7 @@ ulimit -c 0
 cd "$GRAFT_REPO_ROOT" || exit 1
 mkdir -p gpurun_out; out=gpurun_out/small${TAG:+_$TAG}.txt; : > $out
 for n in ${SIZES:-256 500 512 1000 1024}; do
-  timeout 300 python3 bench.py --size $n --steps 40 --warmup 5 --no-cpu --no-f64 2>/dev/null | N=$n python3 -c "
+  timeout 300 python3 bench.py --full --size $n --steps 40 --warmup 5 --no-cpu --no-f64 2>/dev/null | N=$n python3 -c "
 import json,sys,os
 d=json.loads(sys.stdin.read().strip().splitlines()[-1])
 k=d['kernels']

@@ -6,7 +6,7 @@ n=${1:-4096}; dt=${2:-f32}
 out=gpurun_out/timeline; mkdir -p $out
 ROOT=$PWD
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $ROOT/$out/kt -- python3 $ROOT/bench.py --size $n --dtype $dt --steps 8 --warmup 2 --no-cpu --no-f64 --no-pipeline > $ROOT/$out/log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $ROOT/$out/kt -- python3 $ROOT/bench.py --full --size $n --dtype $dt --steps 8 --warmup 2 --no-cpu --no-f64 --no-pipeline > $ROOT/$out/log 2>&1
 cd $ROOT
 f=$(ls $out/kt/*/*kernel_trace.csv | head -1)
 python3 - $f > $out/timeline_${n}_$dt.txt <<'PY'

@@ -3,7 +3,7 @@
 out=gpurun_out/trace512; mkdir -p $out
 ROOT=$PWD
 cd /tmp && export TMPDIR=/tmp
-rocprofv3 --kernel-trace --output-format csv -d $ROOT/$out/kt -- python3 $ROOT/bench.py --size ${1:-512} --steps 6 --warmup 2 --no-cpu --no-f64 > $ROOT/$out/log 2>&1
+rocprofv3 --kernel-trace --output-format csv -d $ROOT/$out/kt -- python3 $ROOT/bench.py --full --size ${1:-512} --steps 6 --warmup 2 --no-cpu --no-f64 > $ROOT/$out/log 2>&1
 cd $ROOT
 f=$(ls $out/kt/*/*kernel_trace.csv | head -1)
 python3 - $f <<'PY'

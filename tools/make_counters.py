@@ -48,7 +48,7 @@ for k, cs in acc.items():
         if c in m:
             row[c] = int(m[c])
     out[k] = row
-out['_note'] = ('per WORKING launch, rocprofv3 --pmc separate passes of `python bench.py --no-cpu --no-f64` (4096^2, 3x16, f32); '
+out['_note'] = ('per WORKING launch, rocprofv3 --pmc separate passes of `python bench.py --full --no-cpu --no-f64` (4096^2, 3x16, f32); '
                 'hbm_bytes = (2 x FETCH_SIZE + WRITE_SIZE) KB x 1024 (FETCH_SIZE doubled per MI355X_MICROARCH.md for gfx950)')
 import datetime
 sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), '..'))
@@ -56,6 +56,6 @@ from bench import csrc_sha256   # the kernel sources these counters belong to: b
 out['_meta'] = {'commit': os.environ.get('COMMIT', 'unknown'), 'csrc_sha256': csrc_sha256(), 'date': datetime.date.today().isoformat(),
                 'config': {'n': int(os.environ.get('PMC_SIZE', '4096')), 'K': int(os.environ.get('PMC_K', '16')),
                            'dtype': os.environ.get('PMC_DTYPE', 'f32')},
-                'how': 'rocprofv3 --pmc, one pass per counter set, bench.py --steps 2 --warmup 1 --no-cpu --no-f64'}
+                'how': 'rocprofv3 --pmc, one pass per counter set, bench.py --full --steps 2 --warmup 1 --no-cpu --no-f64'}
 json.dump(out, open(sys.argv[1], 'w'), indent=1, sort_keys=True)
 print(json.dumps(out, indent=1, sort_keys=True))
