@@ -459,6 +459,10 @@ class Plan:
         check(self.lib.gpa_find_peaks_dev(self.handle, _ptr(int(image_ptr)), float(sigma), float(dog_sigma),
                                           float(threshold_rel), int(max_out), _ptr(coords), _ptr(vals), C.byref(count),
                                           _ptr(None if smooth_ptr is None else int(smooth_ptr))), 'gpa_find_peaks_dev')
+        if count.value > max_out:
+            # the first max_out candidates in the device's atomic-append order are an arbitrary subset: fetch them all from
+            # the smoothed spectrum the plan now holds, as find_peaks retries
+            return self.find_peaks_again(threshold_rel, max_out=count.value)
         n = min(count.value, max_out)
         coords, vals = coords[:n], vals[:n]
         order = np.lexsort((coords[:, 1], coords[:, 0], -vals))

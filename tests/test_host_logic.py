@@ -68,3 +68,58 @@ def test_generate_klists_matches_reference(golden):
     # unsorted: the same points in grid order
     raw = GPA.generate_klists(g['kvecs'], kmax=1.12, kmin=0.9)[1]
     assert sorted(map(tuple, raw)) == sorted(map(tuple, g['wfr4_ring']))
+
+
+class _FakePeaksLib:
+    """stands in for libgpa_hip.so's two candidate-list entry points: the device's list is `cands` (rows of (row, col,
+    value)) in an arbitrary atomic-append order; a call stores the first max_out of them and reports the full count"""
+
+    def __init__(self, cands, dtype):
+        self.cands, self.dtype, self.calls = cands, dtype, []
+
+    def _store(self, max_out, coords, values, count):
+        import ctypes as C
+        n = min(len(self.cands), max_out)
+        c = np.ctypeslib.as_array((C.c_int32 * (2 * max_out)).from_address(coords.value)).reshape(max_out, 2)
+        v = np.frombuffer((C.c_char * (max_out * np.dtype(self.dtype).itemsize)).from_address(values.value), dtype=self.dtype)
+        c[:n] = self.cands[:n, :2]
+        v[:n] = self.cands[:n, 2]
+        count._obj.value = len(self.cands)
+        return 0
+
+    def gpa_find_peaks_dev(self, handle, image, sigma, dog_sigma, thr, max_out, coords, values, count, smooth):
+        self.calls.append(('dev', thr, max_out))
+        return self._store(max_out, coords, values, count)
+
+    def gpa_find_peaks_again(self, handle, thr, max_out, coords, values, count):
+        self.calls.append(('again', thr, max_out))
+        return self._store(max_out, coords, values, count)
+
+    def gpa_plan_destroy(self, handle):
+        pass
+
+
+@pytest.mark.parametrize('dtype', [np.float32, np.float64])
+def test_find_peaks_dev_fetches_every_candidate(dtype):
+    """find_peaks_dev used to keep the first max_out candidates of a longer list -- the device's append
+    order, an arbitrary subset.  A count above max_out must lead to a second fetch of `count` entries from the plan's
+    smoothed spectrum (gpa_find_peaks_again at the same threshold), sorted like find_peaks (highest first, raster order
+    among equals); a count within max_out is taken as it is"""
+    from pygpa_amd import _lib
+    rng = np.random.default_rng(3)
+    rc = rng.choice(64 * 64, size=40, replace=False)
+    vals = rng.integers(1, 8, size=40).astype(dtype)          # many equal values: the raster tie order matters
+    cands = np.column_stack([rc // 64, rc % 64, vals]).astype(np.float64)
+    plan = _lib.Plan.__new__(_lib.Plan)
+    plan.handle, plan.shape, plan.rdtype = 1, (64, 64), dtype
+    plan.lib = _FakePeaksLib(cands, dtype)
+    coords, values = plan.find_peaks_dev(0x1000, 1.0, 0.0, 0.25, max_out=16)
+    assert plan.lib.calls == [('dev', 0.25, 16), ('again', 0.25, 40)]
+    order = np.lexsort((cands[:, 1], cands[:, 0], -cands[:, 2]))
+    assert np.array_equal(coords, cands[order, :2].astype(np.intp)) and coords.dtype == np.intp
+    assert np.array_equal(values, cands[order, 2].astype(dtype)) and values.dtype == dtype
+    plan.lib.calls = []
+    coords2, values2 = plan.find_peaks_dev(0x1000, 1.0, 0.0, 0.25, max_out=40)
+    assert plan.lib.calls == [('dev', 0.25, 40)]
+    assert np.array_equal(coords2, coords) and np.array_equal(values2, values)
+    plan.handle = None
