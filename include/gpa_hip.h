@@ -394,6 +394,38 @@ int gpa_find_peaks_dev(gpa_plan* plan, const void* d_image, double sigma, double
 int gpa_find_peaks_again(gpa_plan* plan, double threshold_rel, int max_out, int32_t* coords, void* values,
                          int* count_out);
 
+/* Unit-cell averaging and expansion (unit_cell_averaging.py).  The geometry is computed on the host exactly as
+ * the reference computes it: ks = the first two k-vectors (cycles / pixel, row-major 2 x 2), kinv = np.linalg.inv(ks),
+ * (rmin, rsize) = calc_ucell_parameters(ks, z).  rsize[0] x rsize[1] <= 2^24 bins (GPA_ERR_STATE beyond).        */
+typedef struct gpa_ucell_geom {
+  double ks[4];
+  double kinv[4];
+  double rmin[2];
+  int32_t rsize[2];
+  double z;
+} gpa_ucell_geom;
+/* unit_cell_average (unit_cell_averaging.py:132-205): every pixel of the plan-shaped image lands at
+ * z (cart_in_uc(r + u(r)) - rmin) and adds value * overlap and overlap to the 2 x 2 bins around it; res = sums / weights
+ * (NaN where nothing landed), weights (nullable) = the overlap sums.  NaN image pixels and NaN u are skipped.  u: 2 x n0 x
+ * n1 (plan dtype) or NULL for none; res, weights: rsize[0] x rsize[1] DOUBLES in both precisions (summed in f64).
+ * Edges: a corner at index rsize is dropped (the reference raises IndexError there); a corner at -1 lands in the last
+ * row / column, as NumPy indexes.  The result is the same bits on every call.                                        */
+int gpa_unit_cell_average(gpa_plan* plan, const void* image, const void* u, const gpa_ucell_geom* geom, double* res,
+                          double* weights);
+int gpa_unit_cell_average_dev(gpa_plan* plan, const void* image_dev, const void* u_dev, const gpa_ucell_geom* geom,
+                              double* res_dev, double* weights_dev);
+/* B frames (B x n0 x n1, contiguous; 1 <= B <= 65535, else GPA_ERR_ARG) that share u: the pixel lists are built
+ * once; res, weights: B x rsize.  Frame b's result is bitwise what gpa_unit_cell_average_dev gives for it alone.  */
+int gpa_unit_cell_average_batch_dev(gpa_plan* plan, const void* images_dev, int B, const void* u_dev,
+                                    const gpa_ucell_geom* geom, double* res_dev, double* weights_dev);
+/* expand_unitcell (unit_cell_averaging.py:236-251): out(r) = nan_to_num(cell) sampled at z cart_in_uc(r / z2 + u(r))
+ * (order-3 B-spline, mode 'constant', cval 0; f64 arithmetic in both precisions).  cell: rsize[0] x rsize[1] doubles;
+ * u: 2 x n0 x n1 (plan dtype) or NULL for none; out: n0 x n1 (plan dtype), the plan's shape.                          */
+int gpa_expand_unitcell(gpa_plan* plan, const double* cell, const gpa_ucell_geom* geom, double z2, const void* u,
+                        void* out);
+int gpa_expand_unitcell_dev(gpa_plan* plan, const double* cell_dev, const gpa_ucell_geom* geom, double z2,
+                            const void* u_dev, void* out_dev);
+
 /* timing hooks used by bench.py: elapsed milliseconds between two recorded
  * events on the plan's stream (HIP events, so it measures the stream the
  * kernels are launched on).                                                   */

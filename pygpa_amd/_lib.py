@@ -15,6 +15,7 @@ _HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.environ.get('GPA_HIP_LIB') or os.path.join(_HERE, 'libgpa_hip.so')
 
 GPA_F32, GPA_F64 = 0, 1
+UCELL_MAX_FRAMES = 65535     # frames of one gpa_unit_cell_average_batch_dev call
 _DTYPES = {GPA_F32: (np.float32, np.complex64), GPA_F64: (np.float64, np.complex128)}
 
 # every symbol of include/gpa_hip.h: name -> (restype, argtypes)
@@ -87,6 +88,11 @@ SIGNATURES = {
     'gpa_find_peaks': (_i, [_vp, _vp, _d, _d, _d, _i, _vp, _vp, _ip, _vp]),
     'gpa_find_peaks_dev': (_i, [_vp, _vp, _d, _d, _d, _i, _vp, _vp, _ip, _vp]),
     'gpa_find_peaks_again': (_i, [_vp, _d, _i, _vp, _vp, _ip]),
+    'gpa_unit_cell_average': (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    'gpa_unit_cell_average_dev': (_i, [_vp, _vp, _vp, _vp, _vp, _vp]),
+    'gpa_unit_cell_average_batch_dev': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
+    'gpa_expand_unitcell': (_i, [_vp, _vp, _vp, _d, _vp, _vp]),
+    'gpa_expand_unitcell_dev': (_i, [_vp, _vp, _vp, _d, _vp, _vp]),
     'gpa_timer_start': (_i, [_vp]),
     'gpa_timer_stop': (_i, [_vp, _vp]),
     'gpa_set_profiling': (_i, [_vp, _i]),
@@ -98,6 +104,22 @@ SIGNATURES = {
 
 _lib = None
 _lock = threading.Lock()
+
+
+class UcellGeom(C.Structure):
+    """gpa_ucell_geom: the geometry of unit_cell_average / expand_unitcell, computed on the host as the reference does"""
+    _fields_ = [('ks', C.c_double * 4), ('kinv', C.c_double * 4), ('rmin', C.c_double * 2), ('rsize', C.c_int32 * 2),
+                ('z', C.c_double)]
+
+    @classmethod
+    def make(cls, ks, kinv, rmin, rsize, z):
+        g = cls()
+        g.ks[:] = [float(v) for v in np.asarray(ks, dtype=np.float64).reshape(4)]
+        g.kinv[:] = [float(v) for v in np.asarray(kinv, dtype=np.float64).reshape(4)]
+        g.rmin[:] = [float(v) for v in np.asarray(rmin, dtype=np.float64).reshape(2)]
+        g.rsize[:] = [int(v) for v in rsize]
+        g.z = float(z)
+        return g
 
 
 class GPAError(RuntimeError):
@@ -345,6 +367,48 @@ class Plan:
         out = np.empty(self.shape, dtype=self.rdtype)
         check(self.lib.gpa_undistort_image(self.handle, _ptr(deformed), _ptr(u), _ptr(out)), 'gpa_undistort_image')
         return out
+
+    # ---- unit-cell averaging / expansion (unit_cell_averaging.py); geom: a UcellGeom -------------------------
+    def unit_cell_average(self, image, geom, u=None, want_weights=False):
+        """res (and weights) of unit_cell_average: rsize float64 arrays whatever the plan's precision"""
+        image = self._img(image)
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=self.rdtype)
+            if u.shape != (2,) + self.shape:
+                raise ValueError('u must have shape (2,) + plan shape')
+        rs = tuple(geom.rsize)
+        res = np.empty(rs, dtype=np.float64)
+        w = np.empty(rs, dtype=np.float64) if want_weights else None
+        check(self.lib.gpa_unit_cell_average(self.handle, _ptr(image), _ptr(u), C.byref(geom), _ptr(res), _ptr(w)),
+              'gpa_unit_cell_average')
+        return (res, w) if want_weights else res
+
+    def unit_cell_average_dev(self, images_ptr, geom, res_ptr, u_ptr=None, weights_ptr=None, nframes=1):
+        """unit_cell_average of nframes plan-shaped frames (contiguous) sharing u, on device pointers, enqueued on the plan's
+        stream; res / weights: nframes x rsize doubles"""
+        check(self.lib.gpa_unit_cell_average_batch_dev(self.handle, _ptr(int(images_ptr)), int(nframes),
+                                                       _ptr(None if u_ptr is None else int(u_ptr)), C.byref(geom),
+                                                       _ptr(int(res_ptr)), _ptr(None if weights_ptr is None else int(weights_ptr))),
+              'gpa_unit_cell_average_batch_dev')
+
+    def expand_unitcell(self, cell, geom, z2=1, u=None):
+        """expand_unitcell onto the plan's grid: cell is rsize (taken as float64), out is plan-shaped in the plan's dtype"""
+        cell = np.ascontiguousarray(cell, dtype=np.float64)
+        if cell.shape != tuple(geom.rsize):
+            raise ValueError('cell shape %s does not match rsize %s' % (cell.shape, tuple(geom.rsize)))
+        if u is not None:
+            u = np.ascontiguousarray(u, dtype=self.rdtype)
+            if u.shape != (2,) + self.shape:
+                raise ValueError('u must have shape (2,) + plan shape')
+        out = np.empty(self.shape, dtype=self.rdtype)
+        check(self.lib.gpa_expand_unitcell(self.handle, _ptr(cell), C.byref(geom), float(z2), _ptr(u), _ptr(out)),
+              'gpa_expand_unitcell')
+        return out
+
+    def expand_unitcell_dev(self, cell_ptr, geom, out_ptr, z2=1, u_ptr=None):
+        check(self.lib.gpa_expand_unitcell_dev(self.handle, _ptr(int(cell_ptr)), C.byref(geom), float(z2),
+                                               _ptr(None if u_ptr is None else int(u_ptr)), _ptr(int(out_ptr))),
+              'gpa_expand_unitcell_dev')
 
     @staticmethod
     def _rects(rects):

@@ -253,6 +253,7 @@ void gpa_plan_destroy(gpa_plan* p) {
   if (p->ev_x) hipEventDestroy(p->ev_x);
   if (p->d_tsum_part) (void)hipFree(p->d_tsum_part);
   warp_ws_free(&p->warp);
+  ucell_ws_free(&p->ucell);
   dft_axis_destroy(&p->bx0);
   dft_axis_destroy(&p->bx1);
   dft_work_free(&p->dftw);

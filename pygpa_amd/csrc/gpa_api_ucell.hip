@@ -1,0 +1,107 @@
+// C ABI: unit-cell averaging and expansion (unit_cell_averaging.py:132-251), kernels in gpa_ucell.hip.
+//
+// The _dev entry points take device pointers and enqueue on the plan's stream without a host synchronisation (the
+// scratch grows with one, the first time a shape or cell needs more); the host-pointer ones are these plus the copies.
+#include "gpa_plan.h"
+
+static int check_geom(const gpa_plan* p, const gpa_ucell_geom* gg, const char* who, UcellGeom* g) {
+  if (!gg) return fail(GPA_ERR_ARG, std::string(who) + ": null geometry");
+  const long long rs0 = gg->rsize[0], rs1 = gg->rsize[1];
+  if (rs0 < 1 || rs1 < 1 || !(gg->z > 0.0))
+    return fail(GPA_ERR_ARG, std::string(who) + ": need rsize >= 1 per axis and z > 0");
+  if (rs0 * rs1 > UCELL_MAX_BINS)
+    return fail(GPA_ERR_STATE, std::string(who) + ": a cell of " + std::to_string(rs0) + " x " + std::to_string(rs1) +
+                                   " bins is beyond this build's limit of 2^24 (16777216) bins");
+  if ((size_t)p->n0 * p->n1 >= ((size_t)1 << 31))
+    return fail(GPA_ERR_STATE, std::string(who) + ": images of 2^31 pixels or more are beyond the int32 pixel lists");
+  for (int k = 0; k < 4; ++k) {
+    g->ks[k] = gg->ks[k];
+    g->kinv[k] = gg->kinv[k];
+  }
+  g->rmin[0] = gg->rmin[0];
+  g->rmin[1] = gg->rmin[1];
+  g->z = gg->z;
+  g->rs0 = (int)rs0;
+  g->rs1 = (int)rs1;
+  return GPA_OK;
+}
+
+int gpa_unit_cell_average_batch_dev(gpa_plan* p, const void* images_dev, int B, const void* u_dev, const gpa_ucell_geom* geom,
+                                    double* res_dev, double* weights_dev) {
+  if (!p || !images_dev || !res_dev) return fail(GPA_ERR_ARG, "gpa_unit_cell_average: null argument");
+  if (B < 1 || B > UCELL_MAX_FRAMES)
+    return fail(GPA_ERR_ARG, "gpa_unit_cell_average_batch_dev: need 1 <= B <= " + std::to_string(UCELL_MAX_FRAMES) +
+                                 " frames per call (B = " + std::to_string(B) + "; split the stack)");
+  UcellGeom g;
+  TRY(check_geom(p, geom, "gpa_unit_cell_average", &g));
+  HIP_TRY(hipSetDevice(p->device));
+  p->ucell.counted = &p->ws_bytes;
+  ProfInstall prof(p);
+  const hipError_t e = ucell_average(p->dtype, images_dev, B, u_dev, p->n0, p->n1, g, res_dev, weights_dev, p->stream, &p->ucell);
+  if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_unit_cell_average: ") + hipGetErrorString(e));
+  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
+  return GPA_OK;
+}
+
+int gpa_unit_cell_average_dev(gpa_plan* p, const void* image_dev, const void* u_dev, const gpa_ucell_geom* geom, double* res_dev,
+                              double* weights_dev) {
+  return gpa_unit_cell_average_batch_dev(p, image_dev, 1, u_dev, geom, res_dev, weights_dev);
+}
+
+int gpa_unit_cell_average(gpa_plan* p, const void* image, const void* u, const gpa_ucell_geom* geom, double* res, double* weights) {
+  if (!p || !image || !res) return fail(GPA_ERR_ARG, "gpa_unit_cell_average: null argument");
+  UcellGeom g;
+  TRY(check_geom(p, geom, "gpa_unit_cell_average", &g));
+  HIP_TRY(hipSetDevice(p->device));
+  const size_t npx = (size_t)p->n0 * p->n1, ncell = (size_t)g.rs0 * g.rs1;
+  HIP_TRY(hipMemcpyAsync(p->d_image, image, npx * p->rsz, hipMemcpyHostToDevice, p->stream));
+  if (u) HIP_TRY(hipMemcpyAsync(p->d_u, u, 2 * npx * p->rsz, hipMemcpyHostToDevice, p->stream));
+  p->ucell.counted = &p->ws_bytes;
+  void* stage = nullptr;
+  HIP_TRY(ucell_stage(&p->ucell, 2 * ncell * sizeof(double), p->stream, &stage));
+  double* d_out = (double*)stage;
+  int rc = gpa_unit_cell_average_dev(p, p->d_image, u ? p->d_u : nullptr, geom, d_out, weights ? d_out + ncell : nullptr);
+  hipError_t e = hipSuccess;
+  if (rc == GPA_OK) e = hipMemcpyAsync(res, d_out, ncell * sizeof(double), hipMemcpyDeviceToHost, p->stream);
+  if (rc == GPA_OK && e == hipSuccess && weights)
+    e = hipMemcpyAsync(weights, d_out + ncell, ncell * sizeof(double), hipMemcpyDeviceToHost, p->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+  if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_unit_cell_average: ") + hipGetErrorString(e));
+  return rc;
+}
+
+int gpa_expand_unitcell_dev(gpa_plan* p, const double* cell_dev, const gpa_ucell_geom* geom, double z2, const void* u_dev,
+                            void* out_dev) {
+  if (!p || !cell_dev || !out_dev) return fail(GPA_ERR_ARG, "gpa_expand_unitcell: null argument");
+  if (!(z2 > 0.0)) return fail(GPA_ERR_ARG, "gpa_expand_unitcell: need z2 > 0");
+  UcellGeom g;
+  TRY(check_geom(p, geom, "gpa_expand_unitcell", &g));
+  HIP_TRY(hipSetDevice(p->device));
+  p->ucell.counted = &p->ws_bytes;
+  ProfInstall prof(p);
+  const hipError_t e = ucell_expand(p->dtype, cell_dev, g, z2, u_dev, p->n0, p->n1, out_dev, p->stream, &p->ucell);
+  if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_expand_unitcell: ") + hipGetErrorString(e));
+  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
+  return GPA_OK;
+}
+
+int gpa_expand_unitcell(gpa_plan* p, const double* cell, const gpa_ucell_geom* geom, double z2, const void* u, void* out) {
+  if (!p || !cell || !out) return fail(GPA_ERR_ARG, "gpa_expand_unitcell: null argument");
+  UcellGeom g;
+  TRY(check_geom(p, geom, "gpa_expand_unitcell", &g));
+  HIP_TRY(hipSetDevice(p->device));
+  const size_t npx = (size_t)p->n0 * p->n1, ncell = (size_t)g.rs0 * g.rs1;
+  p->ucell.counted = &p->ws_bytes;
+  void* stage = nullptr;
+  HIP_TRY(ucell_stage(&p->ucell, ncell * sizeof(double), p->stream, &stage));
+  double* d_cell = (double*)stage;
+  void* d_out = p->d_wnorm;   // (n0 x n1 reals of the plan)
+  int rc = GPA_OK;
+  hipError_t e = hipMemcpyAsync(d_cell, cell, ncell * sizeof(double), hipMemcpyHostToDevice, p->stream);
+  if (e == hipSuccess && u) e = hipMemcpyAsync(p->d_u, u, 2 * npx * p->rsz, hipMemcpyHostToDevice, p->stream);
+  if (e == hipSuccess) rc = gpa_expand_unitcell_dev(p, d_cell, geom, z2, u ? p->d_u : nullptr, d_out);
+  if (e == hipSuccess && rc == GPA_OK) e = hipMemcpyAsync(out, d_out, npx * p->rsz, hipMemcpyDeviceToHost, p->stream);
+  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
+  if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_expand_unitcell: ") + hipGetErrorString(e));
+  return rc;
+}

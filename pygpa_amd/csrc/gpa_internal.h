@@ -289,5 +289,38 @@ hipError_t warp_invert_u(int dtype, const void* d_u, int n0, int n1, double scal
                          void* d_out, hipStream_t s, int mode, int nan_last, WarpWs* ws, const int* rects = nullptr, int nrect = 0);
 hipError_t warp_image(int dtype, const void* d_img, const void* d_uinv, int n0, int n1, void* d_out, hipStream_t s, WarpWs* ws,
                       const int* rects = nullptr, int nrect = 0);
+// coefficients of an n0 x n1 f64 field for order-3 mode='constant' sampling (gpa_spline.h: interp_constant); d_tmp: n0 x n1
+hipError_t spline_coef_constant_f64(const double* d_in, int n0, int n1, double* d_tmp, double* d_out, hipStream_t s, WarpWs* ws);
+
+// ---- unit-cell averaging and expansion (gpa_ucell.hip) -------------------------------------------------------------
+// geometry of unit_cell_average / expand_unitcell (unit_cell_averaging.py): the k-vector matrix, its inverse, the cell's
+// origin and size in upscaled bins, the upscaling z -- all computed on the host exactly as the reference computes them
+struct UcellGeom {
+  double ks[4], kinv[4], rmin[2], z;
+  int rs0, rs1;
+};
+// scratch of the average (sorted pixel lists, per-list sums) and of the expansion (the cell's spline coefficients),
+// kept by the plan and grown on first use
+struct UcellWs {
+  void* buf = nullptr;
+  size_t cap = 0;
+  WarpWs spline{};             // prefilter taps (buf unused)
+  void* stage = nullptr;       // device staging of the host-pointer entry points
+  size_t stage_cap = 0;
+  size_t* counted = nullptr;
+};
+void ucell_ws_free(UcellWs* ws);
+// the staging buffer of ws, at least `bytes` (grown with a stream synchronisation when a call needs more)
+hipError_t ucell_stage(UcellWs* ws, size_t bytes, hipStream_t s, void** out);
+// frames of one batched average: gridDim.y of its sum and finish kernels
+constexpr int UCELL_MAX_FRAMES = 65535;
+// bins of the cell (rs0 x rs1) a plan supports: the keys are int32 with room for the border row and column
+constexpr long long UCELL_MAX_BINS = 1LL << 24;
+// images: B x n0 x n1 (dtype), u: 2 x n0 x n1 or null; res, weights (nullable): B x rs0 x rs1 doubles.  Enqueued on s.
+hipError_t ucell_average(int dtype, const void* d_images, int B, const void* d_u, int n0, int n1, const UcellGeom& g,
+                         double* d_res, double* d_weights, hipStream_t s, UcellWs* ws);
+// cell: rs0 x rs1 doubles; u: 2 x n0 x n1 (dtype) or null; out: n0 x n1 (dtype).  Enqueued on s.
+hipError_t ucell_expand(int dtype, const double* d_cell, const UcellGeom& g, double z2, const void* d_u, int n0, int n1,
+                        void* d_out, hipStream_t s, UcellWs* ws);
 
 }  // namespace gpa

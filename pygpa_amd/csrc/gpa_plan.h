@@ -200,6 +200,7 @@ struct gpa_plan {
   void* d_peaksmooth = nullptr;   // f-3: the smoothed spectrum of the last gpa_find_peaks call, n0 x n1 reals (gpa_find_peaks_again)
   bool peaks_smooth_valid = false;
   WarpWs warp{};                  // scratch + taps of the Lawler-Fujita kernels (gpa_warp.hip), grown on first use
+  UcellWs ucell{};                // scratch of unit-cell averaging / expansion (gpa_ucell.hip), grown on first use
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool profiling = false;

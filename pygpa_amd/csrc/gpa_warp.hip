@@ -16,31 +16,13 @@
 #include <math.h>
 
 #include "gpa_internal.h"
+#include "gpa_spline.h"
 
 namespace gpa {
 
 namespace {
 
-// taps on each side of the prefilter: the pole is z = sqrt(3) - 2, |z|^k falls below the precision's rounding of the
-// centre tap at k = 16 in f32 (|z|^16 = 7e-10 against 2^-24 = 6e-8) and at k = 28 in f64 (1e-16; 32 kept: |z|^32 = 5e-19)
-template <class T> struct TapHalf { static constexpr int value = sizeof(T) == 4 ? 16 : 32; };
 constexpr int NPAD = 12;     // SciPy's pre-padding for mode='nearest'
-
-enum Ext { EXT_REFLECT = 0, EXT_MIRROR = 1 };
-
-__device__ __forceinline__ int ext_index(int i, int n, int ext) {
-  if (n == 1) return 0;
-  if (ext == EXT_REFLECT) {          // half-sample symmetric: -1 -> 0, n -> n-1
-    const int p = 2 * n;
-    i %= p;
-    if (i < 0) i += p;
-    return i >= n ? p - 1 - i : i;
-  }
-  const int p = 2 * n - 2;           // whole-sample symmetric: -1 -> 1, n -> n-2
-  i %= p;
-  if (i < 0) i += p;
-  return i >= n ? p - i : i;
-}
 
 // FIR along rows (axis 1): one workgroup = FR_OUT consecutive outputs of one row, a thread computes FPT consecutive ones
 // from a register window of FPT + 2 KT inputs (read from the LDS tile once: ~10 LDS reads per output where the
@@ -140,132 +122,6 @@ __global__ __launch_bounds__(256) void fir_cols_kernel(const T* __restrict__ in,
   for (int o = 0; o < 8; ++o) {
     const int r = x0 + g * 8 + o;
     if (r < m0) out[(size_t)r * m1 + y0 + c] = acc[o];
-  }
-}
-
-// cubic B-spline weights as scipy.ndimage evaluates them (ni_splines.c: get_spline_interpolation_weights, order 3).
-// f64: the divisions by 6 as written (pinned to SciPy at 4e-15); f32: times 1/6 -- one instruction where an IEEE
-// division takes ten, six times per round of the fixed point, and 0.5 ulp of f32 either way
-template <class T>
-__device__ __forceinline__ T sixth(T v) {
-  if constexpr (sizeof(T) == 4) return v * T(0.16666666666666666);
-  else return v / T(6);
-}
-template <class T>
-__device__ __forceinline__ void bspline_weights(T t, T (&w)[4]) {
-#pragma clang fp contract(off)   // (the same bits at every call site; SciPy's C evaluates these without fused operations too)
-  const T z = T(1) - t;
-  w[1] = sixth(t * t * (t - T(2)) * T(3) + T(4));
-  w[2] = sixth(z * z * (z - T(2)) * T(3) + T(4));
-  w[0] = sixth(z * z * z);
-  w[3] = T(1) - w[0] - w[1] - w[2];
-}
-// one row of the 4 x 4 tap sum, and its accumulation: explicit fused multiply-adds in ONE fixed order, so that the same taps
-// give the same bits whichever kernel or code path gathers them (from L1 / L2, or from the LDS window of invert_tile_kernel)
-template <class T>
-__device__ __forceinline__ T tap_row(const T (&wy)[4], T t0, T t1, T t2, T t3) {
-#pragma clang fp contract(off)
-  T r = wy[0] * t0;
-  r = fma(wy[1], t1, r);
-  r = fma(wy[2], t2, r);
-  r = fma(wy[3], t3, r);
-  return r;
-}
-// index type of the coefficient gathers: 32-bit element offsets from a uniform base (one address instruction per tap,
-// shared by the two components) while the field is below 2^32 bytes, 64-bit beyond
-template <bool WIDE> struct GatherIdx { typedef unsigned type; };
-template <> struct GatherIdx<true> { typedef size_t type; };
-// element `o` of a field: as base + 32-bit BYTE offset (the form the scalar-base global loads take) or a 64-bit index
-template <class T> __device__ __forceinline__ T gather(const T* __restrict__ base, unsigned o) {
-  return *reinterpret_cast<const T*>(reinterpret_cast<const char*>(base) + (unsigned)(o * (unsigned)sizeof(T)));
-}
-template <class T> __device__ __forceinline__ T gather(const T* __restrict__ base, size_t o) { return base[o]; }
-// four ADJACENT elements from element `o` on: one 16-byte (f64: 32-byte) load -- global memory takes it at 4-byte alignment --
-// where four scalar gathers cost the texture-address unit four wave-instructions (the gathers of a round are bound by that
-// unit, not by bytes)
-template <class T> struct Tap4 { T v[4]; };
-template <class T> __device__ __forceinline__ Tap4<T> gather4(const T* __restrict__ base, unsigned o) {
-  return *reinterpret_cast<const Tap4<T>*>(reinterpret_cast<const char*>(base) + (unsigned)(o * (unsigned)sizeof(T)));
-}
-template <class T> __device__ __forceinline__ Tap4<T> gather4(const T* __restrict__ base, size_t o) {
-  return *reinterpret_cast<const Tap4<T>*>(base + o);
-}
-
-// mode='nearest': coordinate (already shifted by npad) unclamped, tap indices clamped
-template <class T, int NC, bool WIDE = false>
-__device__ __forceinline__ void interp_nearest(const T* const (&coef)[NC], int m0, int m1, T x, T y, T (&out)[NC]) {
-  typedef typename GatherIdx<WIDE>::type I;
-  // keep floor() finite for wild coordinates: everything beyond one sample outside reads the edge
-  x = x < T(-2) ? T(-2) : (x > T(m0 + 1) ? T(m0 + 1) : x);
-  y = y < T(-2) ? T(-2) : (y > T(m1 + 1) ? T(m1 + 1) : y);
-  const T fx = floor(x), fy = floor(y);
-  T wx[4], wy[4];
-  bspline_weights(x - fx, wx);
-  bspline_weights(y - fy, wy);
-  const int ix = (int)fx - 1, iy = (int)fy - 1;
-  int cy[4];
-#pragma unroll
-  for (int b = 0; b < 4; ++b) { const int j = iy + b; cy[b] = j < 0 ? 0 : (j >= m1 ? m1 - 1 : j); }
-#pragma unroll
-  for (int n = 0; n < NC; ++n) out[n] = T(0);
-  // (four scalar gathers per tap row, not one 16-byte load as interp_constant's interior path: measured, the fixed point
-  //  got slower with it -- 13.3 -> 14.5 ms at 16384^2 -- its rounds are bound by instruction issue, not by the gathers)
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    int i = ix + a;
-    i = i < 0 ? 0 : (i >= m0 ? m0 - 1 : i);
-    const I row = (I)i * (I)m1;
-    const I o0 = row + (I)cy[0], o1 = row + (I)cy[1], o2 = row + (I)cy[2], o3 = row + (I)cy[3];
-#pragma unroll
-    for (int n = 0; n < NC; ++n) {
-      const T* cr = coef[n];
-      out[n] = fma(wx[a], tap_row(wy, gather(cr, o0), gather(cr, o1), gather(cr, o2), gather(cr, o3)), out[n]);
-    }
-  }
-}
-
-// mode='constant': whole-sample mirrored taps, `cval` where the coordinate leaves [0, n-1] (NaN coordinates too)
-template <class T, int NC, bool WIDE = false>
-__device__ __forceinline__ void interp_constant(const T* const (&coef)[NC], int n0, int n1, T x, T y, T cval, T (&out)[NC]) {
-  typedef typename GatherIdx<WIDE>::type I;
-  if (!(x >= T(0) && x <= T(n0 - 1) && y >= T(0) && y <= T(n1 - 1))) {
-#pragma unroll
-    for (int n = 0; n < NC; ++n) out[n] = cval;
-    return;
-  }
-  const T fx = floor(x), fy = floor(y);
-  T wx[4], wy[4];
-  bspline_weights(x - fx, wx);
-  bspline_weights(y - fy, wy);
-  const int ix = (int)fx - 1, iy = (int)fy - 1;
-#pragma unroll
-  for (int n = 0; n < NC; ++n) out[n] = T(0);
-  if (ix >= 0 && iy >= 0 && ix + 3 < n0 && iy + 3 < n1) {
-    // the 4 x 4 footprint inside the field -- all but a frame of pixels: no mirror arithmetic (eight integer remainders), the
-    // four taps of a row in one load
-#pragma unroll
-    for (int a = 0; a < 4; ++a) {
-      const I o = (I)(ix + a) * (I)n1 + (I)iy;
-#pragma unroll
-      for (int n = 0; n < NC; ++n) {
-        const Tap4<T> q = gather4(coef[n], o);
-        out[n] = fma(wx[a], tap_row(wy, q.v[0], q.v[1], q.v[2], q.v[3]), out[n]);
-      }
-    }
-    return;
-  }
-  int cy[4];
-#pragma unroll
-  for (int b = 0; b < 4; ++b) cy[b] = ext_index(iy + b, n1, EXT_MIRROR);
-#pragma unroll
-  for (int a = 0; a < 4; ++a) {
-    const I row = (I)ext_index(ix + a, n0, EXT_MIRROR) * (I)n1;
-    const I o0 = row + (I)cy[0], o1 = row + (I)cy[1], o2 = row + (I)cy[2], o3 = row + (I)cy[3];
-#pragma unroll
-    for (int n = 0; n < NC; ++n) {
-      const T* cr = coef[n];
-      out[n] = fma(wx[a], tap_row(wy, gather(cr, o0), gather(cr, o1), gather(cr, o2), gather(cr, o3)), out[n]);
-    }
   }
 }
 
@@ -698,6 +554,13 @@ hipError_t warp_invert_u(int dtype, const void* d_u, int n0, int n1, double scal
                       : invert_constant_t<double>((const double*)d_u, n0, n1, scale, iters, edge, shift, nan_last, (double*)d_out, s, ws, rects, nrect);
   return dtype == 0 ? invert_t<float>((const float*)d_u, n0, n1, (float)scale, iters, edge, shift, (float*)d_out, s, ws, rects, nrect)
                     : invert_t<double>((const double*)d_u, n0, n1, scale, iters, edge, shift, (double*)d_out, s, ws, rects, nrect);
+}
+// order-3 coefficients of an n0 x n1 f64 field for mode='constant' sampling (the whole-sample mirrored prefilter of
+// warp_image), taps kept in ws: the unit cell that expand_unitcell samples (gpa_ucell.hip)
+hipError_t spline_coef_constant_f64(const double* d_in, int n0, int n1, double* d_tmp, double* d_out, hipStream_t s, WarpWs* ws) {
+  const hipError_t e = ensure_taps<double>(ws, s);
+  if (e != hipSuccess) return e;
+  return prefilter<double>(d_in, n0, n1, EXT_MIRROR, (const double*)ws->taps, d_tmp, d_out, s);
 }
 // resample d_img (n0 x n1) at r + u_inv(r), order 3, mode='constant', cval=0
 hipError_t warp_image(int dtype, const void* d_img, const void* d_uinv, int n0, int n1, void* d_out, hipStream_t s, WarpWs* ws,
