@@ -201,6 +201,31 @@ int gpa_extract_displacement_field_async(gpa_plan* plan, const void* image, cons
                                          int kmax, void* u, void* lockins, int32_t* kidx);
 int gpa_last_iters(gpa_plan* plan, int* iters2);
 
+/* The fused driver that also hands out what ONE sweep knows about every peak: extract_displacement_field with
+ * return_gs=True and a gradient sweep as wfr_func -- wfr2_grad_opt / wfr2_grad_vec (geometric_phase_analysis.py:763-836),
+ * cuGPA.wfr2_grad_opt / wfr2_grad_single (cuGPA.py:41-133), the reference's drop-in call (tests/test_cuGPA.py:46-56,
+ * geometric_phase_analysis.py:919-922) -- whose g['grad'] and |g['lockin']| feed property_extract.phasegradient2J
+ * (property_extract.py:69-101).  Arguments as gpa_extract_displacement_field, and
+ *   grad_mode : the stencil of gpa_sweep_grad (0 np.gradient, 1 / 2 forward differences)
+ *   grads     : P x n0 x n1 x 2 phase gradients of the winners (the `grad` of gpa_sweep per peak), nullable
+ *   absw      : P x n0 x n1 reals |lockins| (the weights of phasegradient2J), nullable
+ * lockins and kidx are nullable as before.  With grads != NULL pass B writes the phase of all P K candidates to plan
+ * scratch (P K n0 n1 reals, allocated by the first such call) and one stencil launch serves the P peaks; with grads ==
+ * NULL and absw == NULL the call enqueues exactly the launches of gpa_extract_displacement_field_dev.
+ * The three forms: host pointers; device pointers, synchronising; device pointers, enqueue only (gpa_last_iters). */
+int gpa_extract_displacement_field_grad(gpa_plan* plan, const void* image, const double* kvecs, int P,
+                                        const double* klists, int K, double sigma, int mask_border, int kmax,
+                                        int grad_mode, void* u, void* lockins, int32_t* kidx, void* grads,
+                                        void* absw, int* iters_out);
+int gpa_extract_displacement_field_grad_dev(gpa_plan* plan, const void* image, const double* kvecs, int P,
+                                            const double* klists, int K, double sigma, int mask_border, int kmax,
+                                            int grad_mode, void* u, void* lockins, int32_t* kidx, void* grads,
+                                            void* absw, int* iters_out);
+int gpa_extract_displacement_field_grad_async(gpa_plan* plan, const void* image, const double* kvecs, int P,
+                                              const double* klists, int K, double sigma, int mask_border, int kmax,
+                                              int grad_mode, void* u, void* lockins, int32_t* kidx, void* grads,
+                                              void* absw);
+
 /* A STACK of images of the plan's shape in one call (device pointers; no counterpart in the reference,
  * whose extract_displacement_field (geometric_phase_analysis.py:907-932) takes one image): images
  * B x n0 x n1, u B x 2 x n0 x n1.  The sweep and the least squares run image after image; the 2 B

@@ -57,6 +57,9 @@ SIGNATURES = {
     'gpa_extract_displacement_field_dev': (_i, [_vp, _vp, _vp, _i, _vp, _i, _d, _i, _i, _vp, _vp, _vp, _vp]),
     'gpa_extract_displacement_field_async': (_i, [_vp, _vp, _vp, _i, _vp, _i, _d, _i, _i, _vp, _vp, _vp]),
     'gpa_last_iters': (_i, [_vp, _vp]),
+    'gpa_extract_displacement_field_grad': (_i, [_vp, _vp, _vp, _i, _vp, _i, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gpa_extract_displacement_field_grad_dev': (_i, [_vp, _vp, _vp, _i, _vp, _i, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
+    'gpa_extract_displacement_field_grad_async': (_i, [_vp, _vp, _vp, _i, _vp, _i, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'gpa_extract_displacement_field_batch_dev': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _d, _i, _i, _vp, _vp]),
     'gpa_last_batch_iters': (_i, [_vp, _i, _vp]),
     'gpa_supports_batch': (_i, [_vp]),
@@ -605,7 +608,11 @@ class Plan:
         return phi, iters.value
 
     def extract_displacement_field(self, image, kvecs, klists, sigma, mask_border, kmax=10,
-                                   want_lockins=False, want_kidx=False, out=None):
+                                   want_lockins=False, want_kidx=False, out=None, want_grads=False, want_weights=False,
+                                   grad_mode=0):
+        """The fused driver on host arrays: (u, lockins, kidx, iters).  want_grads / want_weights: the same sweep also gives
+        the winners' phase gradients (P, n0, n1, 2; stencil `grad_mode` as in sweep) and |lockins| (P, n0, n1) -- the return
+        value is then the 6-tuple (u, lockins, kidx, iters, grads, weights), with None for what was not asked for."""
         kvecs = _f64(kvecs).reshape(-1, 2)
         klists = _f64(klists)
         P = len(kvecs)
@@ -613,13 +620,22 @@ class Plan:
         K = klists.shape[1]
         if out is not None and (out.shape != (2,) + self.shape or out.dtype != self.rdtype or not out.flags.c_contiguous):
             raise ValueError('out must be a C-contiguous (2,) + plan shape array of the plan dtype')
-        if not want_lockins and not want_kidx and self.shape[0] * self.shape[1] >= 512 * 512:
+        one_sweep = bool(want_grads or want_weights)
+        if not want_lockins and not want_kidx and not one_sweep and self.shape[0] * self.shape[1] >= 512 * 512:
             return self._extract_host_pipelined(image, kvecs, klists, sigma, mask_border, kmax, out)
         u = out if out is not None else np.empty((2,) + self.shape, dtype=self.rdtype)
         image = self._img(image)
         lock = np.empty((P,) + self.shape, dtype=self.cdtype) if want_lockins else None
         kidx = np.empty((P,) + self.shape, dtype=np.int32) if want_kidx else None
         iters = (C.c_int * 2)()
+        if one_sweep:
+            grads = np.empty((P,) + self.shape + (2,), dtype=self.rdtype) if want_grads else None
+            absw = np.empty((P,) + self.shape, dtype=self.rdtype) if want_weights else None
+            check(self.lib.gpa_extract_displacement_field_grad(self.handle, _ptr(image), _ptr(kvecs), P, _ptr(klists), K,
+                                                               float(sigma), int(mask_border), int(kmax), int(grad_mode),
+                                                               _ptr(u), _ptr(lock), _ptr(kidx), _ptr(grads), _ptr(absw), iters),
+                  'gpa_extract_displacement_field_grad')
+            return u, lock, kidx, (iters[0], iters[1]), grads, absw
         check(self.lib.gpa_extract_displacement_field(self.handle, _ptr(image), _ptr(kvecs), P, _ptr(klists), K,
                                                       float(sigma), int(mask_border), int(kmax), _ptr(u), _ptr(lock),
                                                       _ptr(kidx), iters), 'gpa_extract_displacement_field')
@@ -756,11 +772,20 @@ class Plan:
         return iters.value
 
     def extract_displacement_field_dev(self, image_ptr, kvecs, klists, sigma, mask_border, kmax, u_ptr,
-                                       lockins_ptr=None, kidx_ptr=None):
+                                       lockins_ptr=None, kidx_ptr=None, grads_ptr=None, weights_ptr=None, grad_mode=0):
+        """device pointers; grads_ptr (P x n0 x n1 x 2) / weights_ptr (P x n0 x n1): the winners' phase gradients and
+        |lockins| from the same sweep (gpa_extract_displacement_field_grad_dev); without them the plain driver is called"""
         kvecs = _f64(kvecs).reshape(-1, 2)
         P = len(kvecs)
         klists = _f64(klists).reshape(P, -1, 2)
         iters = (C.c_int * 2)()
+        if grads_ptr is not None or weights_ptr is not None:
+            check(self.lib.gpa_extract_displacement_field_grad_dev(self.handle, _ptr(image_ptr), _ptr(kvecs), P, _ptr(klists),
+                                                                   klists.shape[1], float(sigma), int(mask_border), int(kmax),
+                                                                   int(grad_mode), _ptr(u_ptr), _ptr(lockins_ptr), _ptr(kidx_ptr),
+                                                                   _ptr(grads_ptr), _ptr(weights_ptr), iters),
+                  'gpa_extract_displacement_field_grad_dev')
+            return iters[0], iters[1]
         check(self.lib.gpa_extract_displacement_field_dev(self.handle, _ptr(image_ptr), _ptr(kvecs), P, _ptr(klists),
                                                           klists.shape[1], float(sigma), int(mask_border), int(kmax),
                                                           _ptr(u_ptr), _ptr(lockins_ptr), _ptr(kidx_ptr), iters),
@@ -768,11 +793,18 @@ class Plan:
         return iters[0], iters[1]
 
     def extract_displacement_field_async(self, image_ptr, kvecs, klists, sigma, mask_border, kmax, u_ptr,
-                                         lockins_ptr=None, kidx_ptr=None):
+                                         lockins_ptr=None, kidx_ptr=None, grads_ptr=None, weights_ptr=None, grad_mode=0):
         """enqueue only; pair with sync() / last_iters()"""
         kvecs = _f64(kvecs).reshape(-1, 2)
         P = len(kvecs)
         klists = _f64(klists).reshape(P, -1, 2)
+        if grads_ptr is not None or weights_ptr is not None:
+            check(self.lib.gpa_extract_displacement_field_grad_async(self.handle, _ptr(image_ptr), _ptr(kvecs), P, _ptr(klists),
+                                                                     klists.shape[1], float(sigma), int(mask_border), int(kmax),
+                                                                     int(grad_mode), _ptr(u_ptr), _ptr(lockins_ptr),
+                                                                     _ptr(kidx_ptr), _ptr(grads_ptr), _ptr(weights_ptr)),
+                  'gpa_extract_displacement_field_grad_async')
+            return
         check(self.lib.gpa_extract_displacement_field_async(self.handle, _ptr(image_ptr), _ptr(kvecs), P, _ptr(klists),
                                                             klists.shape[1], float(sigma), int(mask_border), int(kmax),
                                                             _ptr(u_ptr), _ptr(lockins_ptr), _ptr(kidx_ptr)),

@@ -48,15 +48,26 @@ int extract_stage(gpa_plan* p, const double* kvecs, int P, const double* klists,
 }
 
 // every launch of the driver, nothing else: this is what a hipGraph of the call holds
+// grads (P x n0 x n1 x 2) / absw (P x n0 x n1) != NULL: the one-sweep form -- pass B also leaves the phase of every candidate in
+// p->d_sf (sized by the caller), the multi-peak stencil turns them into the winners' phase gradients, |lock-in| goes to absw;
+// the lock-ins are compensated then, kidx is not NULL.  Both NULL: the launches of the plain driver, nothing else.
 int extract_launch(gpa_plan* p, const void* image, int P, int K, int Bx, int mask_border, int kmax, void* u,
-                          void* lk, int32_t* kidx, bool want_lockins) {
+                          void* lk, int32_t* kidx, bool want_lockins, void* grads, void* absw, int grad_mode) {
   const size_t npx = (size_t)p->n0 * p->n1;
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[0], p->stream));
   HIP_TRY(launch_mean(p->dtype, image, npx, p->d_scratch, p->d_mean, p->stream));
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[1], p->stream));
   TRY(run_passA(p, image, p->d_mean, p->Tbuf, Bx));
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[2], p->stream));
-  TRY(passB_select(p, P, K, lk, kidx, !want_lockins));
+  if (grads) {
+    bool shared = false;
+    TRY(passB_phases(p, P, K, lk, kidx, p->d_sf, &shared));
+    HIP_TRY(launch_phasegrad(p->dtype, p->d_sf, K, kidx, p->n0, p->n1, p->d_kl, p->d_kr, grad_mode, grads, p->stream,
+                             shared ? p->d_ystep : nullptr, P));
+  } else {
+    TRY(passB_select(p, P, K, lk, kidx, !want_lockins && !absw));
+  }
+  if (absw) HIP_TRY(launch_cabs(p->dtype, lk, (size_t)P * npx, absw, p->stream));
   const double* ystep = p->lk_raw ? p->d_ystep : nullptr;
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[3], p->stream));
   // phases / weights / per-pixel least squares fused with the unwrap's set-up: the gradient fields never
@@ -117,25 +128,41 @@ int extract_launch(gpa_plan* p, const void* image, int P, int K, int Bx, int mas
 // (Rounds 2-4 could capture them into a hipGraph -- USE_GRAPH=1 -- and replay it: measured NOT faster than eager launches at
 // any size on MI355X / ROCm 7.2, 512^2 0.65 against 0.60 ms, 4096^2 equal, and it serialised with the copy stream of
 // gpa_download_async: profiles/r02_graph_vs_eager.txt.  Removed in round 5; git history has it.)
+// what: the entry point's name for the messages.  grads / absw (nullable): the one-sweep form, see extract_launch
 int extract_enqueue(gpa_plan* p, const void* image, const double* kvecs, int P, const double* klists, int K,
-                           double sigma, int mask_border, int kmax, void* u, void* lockins, int32_t* kidx) {
-  if (!p || !image || !kvecs || !klists || !u) return fail(GPA_ERR_ARG, "gpa_extract_displacement_field: null argument");
-  if (P < 2 || P > p->max_peaks) return fail(GPA_ERR_STATE, "gpa_extract_displacement_field: need 2 <= P <= 8");
-  if (K < 1 || P * K > p->max_batch) return fail(GPA_ERR_STATE, "gpa_extract_displacement_field: P*K exceeds max_batch");
+                           double sigma, int mask_border, int kmax, void* u, void* lockins, int32_t* kidx, void* grads,
+                           void* absw, int grad_mode, const char* what) {
+  const std::string fn(what);
+  if (!p || !image || !kvecs || !klists || !u) return fail(GPA_ERR_ARG, fn + ": null argument");
+  if (P < 2 || P > p->max_peaks) return fail(GPA_ERR_STATE, fn + ": need 2 <= P <= 8");
+  if (K < 1 || P * K > p->max_batch) return fail(GPA_ERR_STATE, fn + ": P*K exceeds max_batch");
   if (kmax < 1) return fail(GPA_ERR_ARG, "kmax must be >= 1");
+  if (grads && (grad_mode < 0 || grad_mode > 2)) return fail(GPA_ERR_ARG, fn + ": grad_mode must be 0, 1 or 2");
   HIP_TRY(hipSetDevice(p->device));
   int Bx = 0;
   TRY(extract_stage(p, kvecs, P, klists, K, sigma, &Bx));
   void* lk = lockins ? lockins : p->d_lockin;
+  if (grads) {
+    // the phases of all P K candidates (reals): allocated by the first call that asks for gradients, kept by the plan
+    TRY(ensure_sf(p, (size_t)P * K * p->n0 * p->n1 * p->rsz));
+    if (!kidx) kidx = p->d_kidx;
+  }
   // per-kernel event pairs while profiling (installed for this thread until the function returns)
   ProfInstall prof(p);
-  return extract_launch(p, image, P, K, Bx, mask_border, kmax, u, lk, kidx, lockins != nullptr);
+  return extract_launch(p, image, P, K, Bx, mask_border, kmax, u, lk, kidx, lockins != nullptr, grads, absw, grad_mode);
 }
 
 int gpa_extract_displacement_field_async(gpa_plan* p, const void* image, const double* kvecs, int P,
                                          const double* klists, int K, double sigma, int mask_border, int kmax,
                                          void* u, void* lockins, int32_t* kidx) {
   return extract_enqueue(p, image, kvecs, P, klists, K, sigma, mask_border, kmax, u, lockins, kidx);
+}
+
+int gpa_extract_displacement_field_grad_async(gpa_plan* p, const void* image, const double* kvecs, int P,
+                                              const double* klists, int K, double sigma, int mask_border, int kmax,
+                                              int grad_mode, void* u, void* lockins, int32_t* kidx, void* grads, void* absw) {
+  return extract_enqueue(p, image, kvecs, P, klists, K, sigma, mask_border, kmax, u, lockins, kidx, grads, absw, grad_mode,
+                         "gpa_extract_displacement_field_grad_async");
 }
 
 // A stack of images of one shape in one call: every kernel of the driver takes an image / problem index from its
@@ -264,16 +291,55 @@ int gpa_last_iters(gpa_plan* p, int* iters2) {
   return GPA_OK;
 }
 
-int gpa_extract_displacement_field_dev(gpa_plan* p, const void* image, const double* kvecs, int P,
-                                       const double* klists, int K, double sigma, int mask_border, int kmax,
-                                       void* u, void* lockins, int32_t* kidx, int* iters_out) {
-  TRY(extract_enqueue(p, image, kvecs, P, klists, K, sigma, mask_border, kmax, u, lockins, kidx));
+// the synchronising end of a driver call: stage / kernel times of a profiled call, iteration counts
+static int extract_finish(gpa_plan* p, int* iters_out) {
   HIP_TRY(hipStreamSynchronize(p->stream));
   if (p->profiling) {
     for (int i = 0; i < 5; ++i) hipEventElapsedTime(&p->stage_ms[i], p->stage_ev[i], p->stage_ev[i + 1]);
     collect_kernel_profile(p);
   }
   if (iters_out) { iters_out[0] = p->h_iters[p->iters_off]; iters_out[1] = p->h_iters[p->iters_stride + p->iters_off]; }
+  return GPA_OK;
+}
+
+int gpa_extract_displacement_field_dev(gpa_plan* p, const void* image, const double* kvecs, int P,
+                                       const double* klists, int K, double sigma, int mask_border, int kmax,
+                                       void* u, void* lockins, int32_t* kidx, int* iters_out) {
+  TRY(extract_enqueue(p, image, kvecs, P, klists, K, sigma, mask_border, kmax, u, lockins, kidx));
+  return extract_finish(p, iters_out);
+}
+
+int gpa_extract_displacement_field_grad_dev(gpa_plan* p, const void* image, const double* kvecs, int P,
+                                            const double* klists, int K, double sigma, int mask_border, int kmax,
+                                            int grad_mode, void* u, void* lockins, int32_t* kidx, void* grads, void* absw,
+                                            int* iters_out) {
+  TRY(extract_enqueue(p, image, kvecs, P, klists, K, sigma, mask_border, kmax, u, lockins, kidx, grads, absw, grad_mode,
+                      "gpa_extract_displacement_field_grad_dev"));
+  return extract_finish(p, iters_out);
+}
+
+int gpa_extract_displacement_field_grad(gpa_plan* p, const void* image, const double* kvecs, int P,
+                                        const double* klists, int K, double sigma, int mask_border, int kmax,
+                                        int grad_mode, void* u, void* lockins, int32_t* kidx, void* grads, void* absw,
+                                        int* iters_out) {
+  if (!p || !image || !u) return fail(GPA_ERR_ARG, "gpa_extract_displacement_field_grad: null argument");
+  if (P < 2 || P > p->max_peaks) return fail(GPA_ERR_STATE, "gpa_extract_displacement_field_grad: need 2 <= P <= 8");
+  HIP_TRY(hipSetDevice(p->device));
+  const size_t npx = (size_t)p->n0 * p->n1;
+  // device staging of the two new outputs, sized for the plan's peaks on the first call that asks for them
+  if (grads && !p->d_grads) TRY(dmalloc(p, &p->d_grads, (size_t)p->max_peaks * 2 * npx * p->rsz));
+  if (absw && !p->d_absw) TRY(dmalloc(p, &p->d_absw, (size_t)p->max_peaks * npx * p->rsz));
+  HIP_TRY(hipMemcpyAsync(p->d_image, image, npx * p->rsz, hipMemcpyHostToDevice, p->stream));
+  TRY(extract_enqueue(p, p->d_image, kvecs, P, klists, K, sigma, mask_border, kmax, p->d_u, lockins ? p->d_lockin : nullptr,
+                      kidx ? p->d_kidx : nullptr, grads ? p->d_grads : nullptr, absw ? p->d_absw : nullptr, grad_mode,
+                      "gpa_extract_displacement_field_grad"));
+  TRY(extract_finish(p, iters_out));
+  HIP_TRY(hipMemcpyAsync(u, p->d_u, 2 * npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
+  if (lockins) HIP_TRY(hipMemcpyAsync(lockins, p->d_lockin, (size_t)P * npx * p->csz, hipMemcpyDeviceToHost, p->stream));
+  if (kidx) HIP_TRY(hipMemcpyAsync(kidx, p->d_kidx, (size_t)P * npx * sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
+  if (grads) HIP_TRY(hipMemcpyAsync(grads, p->d_grads, (size_t)P * 2 * npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
+  if (absw) HIP_TRY(hipMemcpyAsync(absw, p->d_absw, (size_t)P * npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
   return GPA_OK;
 }
 

@@ -70,6 +70,30 @@ int passB_select(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, bool ra
   return GPA_OK;
 }
 
+// pass B of the one-sweep driver: selection for all P peaks of the staged list AND -angle of every candidate's lock-in into
+// psi [P][K][n0][n1] reals, on the x-planes pass A left in Tbuf.  The shared-forward kernel where it takes the rows and the
+// list (*shared = true: its phases lack exp(i ystep_p y), see launch_phasegrad), else the per-candidate kernel in its phases
+// mode.  The lock-ins are compensated either way.
+int passB_phases(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, void* psi, bool* shared) {
+  p->lk_raw = false;
+  *shared = false;
+  if (p->use_shared && !opt_set(OPT_NO_SHARED_PHASES)) {
+    TRY(shared_prepare(p, P, K));
+    if (p->sh_use && p->sh_one_kref) {
+      const hipError_t e = launch_passB_shared_phases(p->dtype, p->ax1s, p->n0, p->Tbuf, p->ax1s.L == p->ax1.L ? p->tw1 : p->tw1s,
+                                                      p->tb, p->sh, p->sh_E, p->sh_Epad, P, K, lockin, kidx, psi, p->stream, 0,
+                                                      p->sh_elems, p->sh_nbl);
+      if (e == hipSuccess) {
+        *shared = true;
+        return GPA_OK;
+      }
+      if (e != hipErrorInvalidValue) return fail(GPA_ERR_HIP, std::string("shared pass B (phases): ") + hipGetErrorString(e));
+    }
+  }
+  HIP_TRY(launch_passB_ext(p->dtype, p->ax1, p->n0, p->Tbuf, p->Hy, p->tw1, p->tb, K, 3, lockin, kidx, nullptr, psi, p->stream, P));
+  return GPA_OK;
+}
+
 // per-kernel event pairs of a profiled call, summed by name in order of first appearance -> p->kprof_table
 void collect_kernel_profile(gpa_plan* p) {
   std::vector<std::string> names;

@@ -180,10 +180,11 @@ hipError_t launch_passB(int dtype, const Axis& a1, int n0, const void* Tbuf, con
                         void* out, int32_t* kidx, hipStream_t s, int nimg = 1, int Bx = 0);
 // one peak, K candidates, the less travelled selection modes (gpa_sweep_ext.hip): mode 2 = gated selection of
 // wfr4 (gate: device K x K bytes, gate[j * K + k] != 0 where candidate k may replace the kept candidate j),
-// mode 3 = plain selection that also writes psi[k][x][y] = -angle(sf_k) of every candidate
+// mode 3 = plain selection that also writes psi[k][x][y] = -angle(sf_k) of every candidate; mode 3 takes P peaks of K staged
+// candidates each in one launch (out / kidx: P planes, psi [P][K][n0][n1])
 hipError_t launch_passB_ext(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* Hy, const void* tw1,
                             const SweepTables& tb, int K, int mode, void* out, int32_t* kidx, const uint8_t* gate,
-                            void* psi, hipStream_t s);
+                            void* psi, hipStream_t s, int P = 1);
 // small images (transform length <= 1024): best-of-K with the K candidates of a row split over ksplit workgroups and a
 // merge pass; part / pidx: ksplit * P * n0 * n1 complex / int32 of scratch.  Same winners and values as launch_passB.
 hipError_t launch_passB_split(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* Hy, const void* tw1,
@@ -193,8 +194,9 @@ hipError_t launch_passB_split(int dtype, const Axis& a1, int n0, const void* Tbu
 // NaN at the end, 2 the same with swapped components)
 // ystep (device, one double) != null: psi holds the phases of the shared pass B (compensated along x, lacking the phasor
 // exp(i ystep y)): no 2 pi (w - k) is added, ystep is subtracted from the differences along y
+// P peaks in one launch: psi [P][K][n0][n1], kidx [P][n0][n1], kl / kr [P K][2], ystep [P], grad [P][n0][n1][2]
 hipError_t launch_phasegrad(int dtype, const void* psi, int K, const int32_t* kidx, int n0, int n1, const double* kl,
-                            const double* kr, int mode, void* grad, hipStream_t s, const double* ystep = nullptr);
+                            const double* kr, int mode, void* grad, hipStream_t s, const double* ystep = nullptr, int P = 1);
 int passA_cols(int dtype, int lg);
 // frequency bin held by (thread, register) after the forward transform of length 2^lg
 int spec_index_rt(int lg, int tid, int reg, int elems = 16);   // elems: elements per thread of the transform (16 or 8)

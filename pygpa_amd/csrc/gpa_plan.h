@@ -163,6 +163,8 @@ struct gpa_plan {
   void* d_sf = nullptr;           // [K][n0][n1] complex, grown on demand (a4 gradient path)
   size_t sf_bytes = 0;
   void* d_grad = nullptr;         // n0 x n1 x 2 staging for the host-pointer a4 call
+  void* d_grads = nullptr;        // [max_peaks] n0 x n1 x 2 and
+  void* d_absw = nullptr;         // [max_peaks] n0 x n1: staging of gpa_extract_displacement_field_grad, allocated on first use
   double* d_scratch = nullptr;    // 16384 doubles (mean partials, Gaussian weights at + 1024, Huber partials: 10 x 1024 + 10)
   void* d_aux0 = nullptr;         // n0 / n1 complex doubles: border-difference spectra (a9), Gaussian factors (f-4);
   void* d_aux1 = nullptr;         // NOT the sweep's compensation tables, which stay valid across those calls
@@ -240,6 +242,7 @@ int ensure_sf(gpa_plan* p, size_t bytes);
 int stage_kmat(gpa_plan* p, const double* kvecs, int P);
 int run_passA(gpa_plan* p, const void* image, const void* mean, void* Tbuf, int Bx, int nimg = 1);
 int passB_select(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, bool raw = false);
+int passB_phases(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, void* psi, bool* shared);
 void collect_kernel_profile(gpa_plan* p);
 int sweep_peaks_dev(gpa_plan* p, const void* image, const void* mean, const double* krefs, int P,
                            const double* klists, int K, double sigma, void* lockin, int32_t* kidx, bool raw = false);
@@ -249,9 +252,12 @@ int sweep_host(gpa_plan* p, const void* image, const double* kref, const double*
                       int grad_mode, const uint8_t* gate, void* lockin, int32_t* kidx, void* grad);
 int extract_stage(gpa_plan* p, const double* kvecs, int P, const double* klists, int K, double sigma, int* Bx);
 int extract_launch(gpa_plan* p, const void* image, int P, int K, int Bx, int mask_border, int kmax, void* u,
-                          void* lk, int32_t* kidx, bool want_lockins);
+                          void* lk, int32_t* kidx, bool want_lockins, void* grads = nullptr, void* absw = nullptr,
+                          int grad_mode = 0);
 int extract_enqueue(gpa_plan* p, const void* image, const double* kvecs, int P, const double* klists, int K,
-                           double sigma, int mask_border, int kmax, void* u, void* lockins, int32_t* kidx);
+                           double sigma, int mask_border, int kmax, void* u, void* lockins, int32_t* kidx,
+                           void* grads = nullptr, void* absw = nullptr, int grad_mode = 0,
+                           const char* what = "gpa_extract_displacement_field");
 int tile_gradients_impl(gpa_plan* p, const void* image, size_t image_pitch, int r0, int c0, bool mean_on_device,
                                double mean, const double* kvecs, int P, const double* klists, int K, double sigma,
                                int mask_border, int i0, int j0, int t0, int t1, void* dx, size_t dx_pitch, size_t dx_plane,

@@ -18,18 +18,22 @@ namespace gpa {
 // then + 2 pi (w - kref) of the matching axis and wrapToPi(2 g) / 2 (:807-812).  wfr2_grad differentiates the
 // phase of the COMPENSATED lock-in and wraps per candidate; that is the same number modulo pi, i.e. the same
 // result up to rounding (tests/test_oracle_golden.py::test_variants_gradient_spellings).
+// The peak comes from the grid (blockIdx.z): psi [P][K][n0][n1], kidx [P][n0][n1], kl / kr at p K + k, ystep[p], grad
+// [P][n0][n1][2] -- one launch for the P peaks of the fused driver; a single sweep is the launch with gridDim.z = 1.
 template <class T>
 __global__ __launch_bounds__(256) void phasegrad_kernel(const T* __restrict__ psi, int K, const int32_t* __restrict__ kidx,
                                                        int n0, int n1, const double* __restrict__ kl,
                                                        const double* __restrict__ kr, int mode, T* __restrict__ grad,
                                                        const double* __restrict__ ystep) {
-  const int y = blockIdx.x * 256 + threadIdx.x, x = blockIdx.y;
+  const int y = blockIdx.x * 256 + threadIdx.x, x = blockIdx.y, p = blockIdx.z;
   if (y >= n1) return;
   const size_t npx = (size_t)n0 * n1, o = (size_t)x * n1 + y;
+  kidx += (size_t)p * npx;
+  grad += (size_t)p * npx * 2;
   const int bi = kidx[o];
   T g0 = T(0), g1 = T(0);
   if (bi >= 0) {
-    const T* pl = psi + (size_t)bi * npx;
+    const T* pl = psi + ((size_t)p * K + bi) * npx;
     const T c = pl[o];
     const T nan = __builtin_nan("");
     if (mode == 0) {
@@ -45,10 +49,11 @@ __global__ __launch_bounds__(256) void phasegrad_kernel(const T* __restrict__ ps
     if (ystep) {
       // compensated form (the shared pass B's phases): psi is -angle of the lock-in compensated along x and lacking only the
       // candidate-independent phasor exp(i ystep y): the compensated phase differs by -ystep per column, and 2 pi (w - k) is in it
-      g1 = (T)((double)g1 - ystep[0]);
+      g1 = (T)((double)g1 - ystep[p]);
     } else {
-      g0 += (T)(6.28318530717958647692 * (kl[2 * bi] - kr[2 * bi]));
-      g1 += (T)(6.28318530717958647692 * (kl[2 * bi + 1] - kr[2 * bi + 1]));
+      const size_t b = (size_t)p * K + bi;
+      g0 += (T)(6.28318530717958647692 * (kl[2 * b] - kr[2 * b]));
+      g1 += (T)(6.28318530717958647692 * (kl[2 * b + 1] - kr[2 * b + 1]));
     }
     // wrapToPi(2 g) / 2 with the floored modulo of mathtools.py:72-75
     const T t0 = T(2) * g0 + pi, t1 = T(2) * g1 + pi;
@@ -60,8 +65,8 @@ __global__ __launch_bounds__(256) void phasegrad_kernel(const T* __restrict__ ps
 }
 
 hipError_t launch_phasegrad(int dtype, const void* psi, int K, const int32_t* kidx, int n0, int n1, const double* kl,
-                            const double* kr, int mode, void* grad, hipStream_t s, const double* ystep) {
-  dim3 grid((n1 + 255) / 256, n0);
+                            const double* kr, int mode, void* grad, hipStream_t s, const double* ystep, int P) {
+  dim3 grid((n1 + 255) / 256, n0, P);
   GPA_PROF("phasegrad_kernel", s);
   if (dtype == 0)
     phasegrad_kernel<float><<<grid, 256, 0, s>>>((const float*)psi, K, kidx, n0, n1, kl, kr, mode, (float*)grad, ystep);
@@ -139,18 +144,19 @@ hipError_t launch_passB_split(int dtype, const Axis& a1, int n0, const void* Tbu
   return hipGetLastError();
 }
 
-// one peak (grid.y = 1), K candidates; mode PB_GATED (gate: device K x K bytes) or PB_PHASES (psi: K x n0 x n1)
+// P peaks (grid.y) of K candidates; mode PB_GATED (one peak; gate: device K x K bytes) or PB_PHASES (psi: P x K x n0 x n1)
 hipError_t launch_passB_ext(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* Hy, const void* tw1,
                             const SweepTables& tb, int K, int mode, void* out, int32_t* kidx, const uint8_t* gate,
-                            void* psi, hipStream_t s) {
+                            void* psi, hipStream_t s, int P) {
 #define CALL_X(T, LG, PD)                                                                                        \
   (mode == PB_GATED ? run_passB<T, LG, PD, PB_GATED>(a1, n0, Tbuf, Hy, tw1, tb, 1, K, out, kidx, gate, psi, s)   \
-                    : run_passB<T, LG, PD, PB_PHASES>(a1, n0, Tbuf, Hy, tw1, tb, 1, K, out, kidx, gate, psi, s))
+                    : run_passB<T, LG, PD, PB_PHASES>(a1, n0, Tbuf, Hy, tw1, tb, P, K, out, kidx, gate, psi, s))
 #define CASE_X(LG)                                                                         \
   case LG:                                                                                 \
     if (dtype == 0) return a1.padded ? CALL_X(float, LG, true) : CALL_X(float, LG, false); \
     else return a1.padded ? CALL_X(double, LG, true) : CALL_X(double, LG, false);
   if (mode != PB_GATED && mode != PB_PHASES) return hipErrorInvalidValue;
+  if (P < 1 || (mode == PB_GATED && P != 1)) return hipErrorInvalidValue;
   switch (a1.lg) { GPA_FOR_LG(CASE_X) }
 #undef CASE_X
 #undef CALL_X

@@ -34,3 +34,9 @@ def wfr2_only_lockin(image, sigma, kvec, kw, kstep):
 def wfr2_only_grad(image, sigma, kvec, kw, kstep, grad=None):
     """cuGPA.py:161-202."""
     return wfr2_grad_opt(image, sigma, kvec[0], kvec[1], kw, kstep, grad=grad)['grad']
+
+
+# plugged into extract_displacement_field as `wfr_func` (reference tests/test_cuGPA.py:46-56) these two are served by the fused
+# driver: the mirror assembles their per-peak results itself (wfr2_grad_single: the device work in f32, no 'w')
+_g.register_native_sweep(wfr2_grad_opt, ('w', 'lockin', 'grad'))
+_g.register_native_sweep(wfr2_grad_single, ('lockin', 'grad'), np.float32)

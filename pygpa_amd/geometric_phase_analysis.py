@@ -194,7 +194,28 @@ def generate_klists(pks, dk=None, kmax=1.9, kmin=0.2, sort_list=False):
     return lists
 
 
-_NATIVE_SWEEPS = (optwfr2, wfr2_grad_opt)
+# Sweep functions whose results the fused driver assembles itself (extract_displacement_field): function -> (the keys of
+# its per-peak result, the dtype its device work is fixed to or None for the call's `dtype`).  A function with 'grad' among
+# its keys is served by the one-sweep form of the driver when return_gs asks for the per-peak results.
+_NATIVE_SWEEPS = {}
+
+
+def register_native_sweep(func, keys, dtype=None):
+    """Declare `func(image, sigma, kx, ky, kw=, kstep=)` a spelling of the np.arange-grid sweep (:669-686, :763-813) whose
+    per-peak mapping holds `keys` (of 'lockin', 'w', 'grad', 'kidx'; gradient stencil np.gradient)."""
+    _NATIVE_SWEEPS[func] = (tuple(keys), dtype)
+
+
+register_native_sweep(optwfr2, ('lockin', 'w', 'kidx'))
+register_native_sweep(wfr2_grad_opt, ('lockin', 'w', 'grad', 'kidx'))
+register_native_sweep(wfr2_grad_vec, ('lockin', 'w', 'grad', 'kidx'))
+
+
+def _native_sweep(wfr_func):
+    try:
+        return _NATIVE_SWEEPS.get(wfr_func)
+    except TypeError:       # an unhashable callable: certainly not one of ours
+        return None
 
 
 # --------------------------------------------------------------------------- f-3
@@ -461,9 +482,11 @@ def extract_displacement_field(image, kvecs, sigma=None, kwscale=2.5, ksteps=3, 
                                wfr_func=optwfr2, deconvolve=False, klists=None, dtype=None):
     """Top level convenience function (geometric_phase_analysis.py:907-932).
 
-    With the package's own sweep functions as ``wfr_func`` the whole chain (mean
+    With the package's own sweep functions as ``wfr_func`` (this module's optwfr2 / wfr2_grad_opt / wfr2_grad_vec, cuGPA's
+    wfr2_grad_opt / wfr2_grad_single) the whole chain (mean
     subtraction, P x K lock-ins, selection, phases/weights, per-pixel least squares,
-    two weighted unwraps) runs in one fused device call; any other callable is
+    two weighted unwraps) runs in one fused device call -- with ``return_gs`` the per-peak results, phase gradients
+    included, come from that same sweep; any other callable (a functools.partial, a user function) is
     invoked per peak exactly like the reference does and only the reconstruction
     runs on the device.  ``klists`` (P lists of (K,2)) replaces the np.arange grid.
     ``deconvolve=True`` Wiener-deconvolves u with the lock-in Gaussian afterwards (:927-928).
@@ -476,21 +499,37 @@ def extract_displacement_field(image, kvecs, sigma=None, kwscale=2.5, ksteps=3, 
         sigma = int(np.ceil(1 / norms.min()))
     kstep = kw / ksteps
     dr = int(2 * sigma)
-    if wfr_func in _NATIVE_SWEEPS and not (return_gs and wfr_func is wfr2_grad_opt):
+    native = _native_sweep(wfr_func)
+    if native is not None:
+        keys, sweep_dtype = native
+        out_dtype = DEFAULT_DTYPE if dtype is None else dtype
         if klists is None:
             klists = [_sweep_list(pk[0], pk[1], kw, kstep) for pk in kvecs]
         klists = [np.asarray(kl, dtype=np.float64).reshape(-1, 2) for kl in klists]
         K = max(len(kl) for kl in klists)
         # lists of unequal length: repeat the last candidate (a repeat can never win a strict '>')
         padded = np.stack([np.concatenate([kl, np.repeat(kl[-1:], K - len(kl), axis=0)]) for kl in klists])
-        plan = _lib.get_plan(image.shape, len(kvecs) * K, DEFAULT_DTYPE if dtype is None else dtype)
-        u, lock, kidx, _ = plan.extract_displacement_field(image, kvecs, padded, sigma, dr, kmax=10,
-                                                           want_lockins=return_gs, want_kidx=return_gs)
+        plan = _lib.get_plan(image.shape, len(kvecs) * K, out_dtype if sweep_dtype is None else sweep_dtype)
+        if return_gs and 'grad' in keys:
+            # one sweep: u and, per peak, lock-in, winner and phase gradient (gpa_extract_displacement_field_grad)
+            u, lock, kidx, _, grads, _ = plan.extract_displacement_field(image, kvecs, padded, sigma, dr, kmax=10,
+                                                                         want_lockins=True, want_kidx=True, want_grads=True)
+        else:
+            grads = None
+            u, lock, kidx, _ = plan.extract_displacement_field(image, kvecs, padded, sigma, dr, kmax=10,
+                                                               want_lockins=return_gs, want_kidx=return_gs)
+        u = np.asarray(u, dtype=out_dtype)
         if deconvolve:
             u = gaussian_deconvolve(u, sigma, dr, dtype=dtype)
         if return_gs:
-            gs = [{'lockin': lock[p], 'w': _w_from_kidx(kidx[p], padded[p]), 'kidx': kidx[p]}
-                  for p in range(len(kvecs))]
+            gs = []
+            for p in range(len(kvecs)):
+                full = {'lockin': lock[p], 'kidx': kidx[p]}
+                if 'w' in keys:
+                    full['w'] = _w_from_kidx(kidx[p], padded[p])
+                if grads is not None:
+                    full['grad'] = grads[p]
+                gs.append({k: full[k] for k in keys})
             return u, gs
         return u
     gs = [wfr_func(image - image.mean(), sigma, pk[0], pk[1], kw=kw, kstep=kstep) for pk in kvecs]
