@@ -205,13 +205,21 @@ class options:
 def _ptr(a):
     if a is None:
         return None
-    if isinstance(a, int):
-        return C.c_void_p(a)
+    if isinstance(a, (int, np.integer)):
+        return C.c_void_p(int(a))
     return a.ctypes.data_as(C.c_void_p)
 
 
 def _f64(a):
     return np.ascontiguousarray(a, dtype=np.float64)
+
+
+def _peak_lists(kvecs, klists):
+    """(kvecs (P, 2), P, klists (P, K, 2), K) as contiguous float64: the reference vectors and candidate lists of a sweep"""
+    kvecs = _f64(kvecs).reshape(-1, 2)
+    P = len(kvecs)
+    klists = _f64(klists).reshape(P, -1, 2)
+    return kvecs, P, klists, klists.shape[1]
 
 
 class Plan:
@@ -390,8 +398,8 @@ class Plan:
         """unit_cell_average of nframes plan-shaped frames (contiguous) sharing u, on device pointers, enqueued on the plan's
         stream; res / weights: nframes x rsize doubles"""
         check(self.lib.gpa_unit_cell_average_batch_dev(self.handle, _ptr(int(images_ptr)), int(nframes),
-                                                       _ptr(None if u_ptr is None else int(u_ptr)), C.byref(geom),
-                                                       _ptr(int(res_ptr)), _ptr(None if weights_ptr is None else int(weights_ptr))),
+                                                       _ptr(u_ptr), C.byref(geom),
+                                                       _ptr(int(res_ptr)), _ptr(weights_ptr)),
               'gpa_unit_cell_average_batch_dev')
 
     def expand_unitcell(self, cell, geom, z2=1, u=None):
@@ -410,7 +418,7 @@ class Plan:
 
     def expand_unitcell_dev(self, cell_ptr, geom, out_ptr, z2=1, u_ptr=None):
         check(self.lib.gpa_expand_unitcell_dev(self.handle, _ptr(int(cell_ptr)), C.byref(geom), float(z2),
-                                               _ptr(None if u_ptr is None else int(u_ptr)), _ptr(int(out_ptr))),
+                                               _ptr(u_ptr), _ptr(int(out_ptr))),
               'gpa_expand_unitcell_dev')
 
     @staticmethod
@@ -436,7 +444,7 @@ class Plan:
         outputs are computed.  scale = -1: u is the field as extract_displacement_field returns it (minus the displacement)"""
         arr, n = self._rects(rects)
         check(self.lib.gpa_undistort_image_scaled_dev(self.handle, _ptr(int(deformed_ptr)), _ptr(int(u_ptr)), float(scale), arr, n,
-                                                      _ptr(None if uinv_ptr is None else int(uinv_ptr)), _ptr(int(out_ptr))),
+                                                      _ptr(uinv_ptr), _ptr(int(out_ptr))),
               'gpa_undistort_image_dev')
 
     def phasegradient2J(self, kvecs, grads, weights, nmperpixel, dks=None):
@@ -458,7 +466,7 @@ class Plan:
         klist = _f64(klist).reshape(-1, 2)
         check(self.lib.gpa_sweep_grad_dev(self.handle, _ptr(int(image_ptr)), _ptr(kref), _ptr(klist), len(klist), float(sigma),
                                           int(grad_mode), _ptr(int(lockin_ptr)),
-                                          _ptr(None if kidx_ptr is None else int(kidx_ptr)), _ptr(int(grad_ptr))),
+                                          _ptr(kidx_ptr), _ptr(int(grad_ptr))),
               'gpa_sweep_grad_dev')
 
     def lockin_weights_dev(self, lockins_ptr, P, weights_ptr):
@@ -525,7 +533,7 @@ class Plan:
         count = C.c_int(0)
         check(self.lib.gpa_find_peaks_dev(self.handle, _ptr(int(image_ptr)), float(sigma), float(dog_sigma),
                                           float(threshold_rel), int(max_out), _ptr(coords), _ptr(vals), C.byref(count),
-                                          _ptr(None if smooth_ptr is None else int(smooth_ptr))), 'gpa_find_peaks_dev')
+                                          _ptr(smooth_ptr)), 'gpa_find_peaks_dev')
         if count.value > max_out:
             # the first max_out candidates in the device's atomic-append order are an arbitrary subset: fetch them all from
             # the smoothed spectrum the plan now holds, as find_peaks retries
@@ -613,11 +621,7 @@ class Plan:
         """The fused driver on host arrays: (u, lockins, kidx, iters).  want_grads / want_weights: the same sweep also gives
         the winners' phase gradients (P, n0, n1, 2; stencil `grad_mode` as in sweep) and |lockins| (P, n0, n1) -- the return
         value is then the 6-tuple (u, lockins, kidx, iters, grads, weights), with None for what was not asked for."""
-        kvecs = _f64(kvecs).reshape(-1, 2)
-        klists = _f64(klists)
-        P = len(kvecs)
-        klists = klists.reshape(P, -1, 2)
-        K = klists.shape[1]
+        kvecs, P, klists, K = _peak_lists(kvecs, klists)
         if out is not None and (out.shape != (2,) + self.shape or out.dtype != self.rdtype or not out.flags.c_contiguous):
             raise ValueError('out must be a C-contiguous (2,) + plan shape array of the plan dtype')
         one_sweep = bool(want_grads or want_weights)
@@ -627,19 +631,29 @@ class Plan:
         image = self._img(image)
         lock = np.empty((P,) + self.shape, dtype=self.cdtype) if want_lockins else None
         kidx = np.empty((P,) + self.shape, dtype=np.int32) if want_kidx else None
+        grads = np.empty((P,) + self.shape + (2,), dtype=self.rdtype) if want_grads else None
+        absw = np.empty((P,) + self.shape, dtype=self.rdtype) if want_weights else None
         iters = (C.c_int * 2)()
-        if one_sweep:
-            grads = np.empty((P,) + self.shape + (2,), dtype=self.rdtype) if want_grads else None
-            absw = np.empty((P,) + self.shape, dtype=self.rdtype) if want_weights else None
-            check(self.lib.gpa_extract_displacement_field_grad(self.handle, _ptr(image), _ptr(kvecs), P, _ptr(klists), K,
-                                                               float(sigma), int(mask_border), int(kmax), int(grad_mode),
-                                                               _ptr(u), _ptr(lock), _ptr(kidx), _ptr(grads), _ptr(absw), iters),
-                  'gpa_extract_displacement_field_grad')
-            return u, lock, kidx, (iters[0], iters[1]), grads, absw
-        check(self.lib.gpa_extract_displacement_field(self.handle, _ptr(image), _ptr(kvecs), P, _ptr(klists), K,
-                                                      float(sigma), int(mask_border), int(kmax), _ptr(u), _ptr(lock),
-                                                      _ptr(kidx), iters), 'gpa_extract_displacement_field')
-        return u, lock, kidx, (iters[0], iters[1])
+        self._extract_call('', image, (kvecs, P, klists, K), sigma, mask_border, kmax, u, lock, kidx, grads, absw, grad_mode, iters)
+        res = (u, lock, kidx, (iters[0], iters[1]))
+        return res + (grads, absw) if one_sweep else res
+
+    def _extract_call(self, form, image, lists, sigma, mask_border, kmax, u, lockins, kidx, grads, absw, grad_mode, iters=None):
+        """the one library call of a driver method, gpa_extract_displacement_field<form> -- its _grad variant (which also takes
+        grad_mode, grads and absw) if and only if grads or absw is asked for.  lists: what _peak_lists returns; the arrays or
+        addresses are host or device ones as `form` takes them; iters: the (C.c_int * 2) of a synchronising form"""
+        kvecs, P, klists, K = lists
+        name = 'gpa_extract_displacement_field'
+        args = [self.handle, _ptr(image), _ptr(kvecs), P, _ptr(klists), K, float(sigma), int(mask_border), int(kmax)]
+        outs = [_ptr(u), _ptr(lockins), _ptr(kidx)]
+        if grads is not None or absw is not None:
+            name += '_grad'
+            args.append(int(grad_mode))
+            outs += [_ptr(grads), _ptr(absw)]
+        if iters is not None:
+            outs.append(iters)
+        name += form
+        check(getattr(self.lib, name)(*args, *outs), name)
 
     def _extract_host_pipelined(self, image, kvecs, klists, sigma, mask_border, kmax, out):
         """The host-array form of the driver with its host work overlapped.  A 4096^2 f32 call spent 18 of its 29 ms on
@@ -674,14 +688,12 @@ class Plan:
 
     def extract_gradients(self, image, kvecs, klists, sigma, mask_border):
         image = self._img(image)
-        kvecs = _f64(kvecs).reshape(-1, 2)
-        P = len(kvecs)
-        klists = _f64(klists).reshape(P, -1, 2)
+        kvecs, P, klists, K = _peak_lists(kvecs, klists)
         n0, n1 = self.shape
         dudx = np.empty((2, n0, n1 - 1), dtype=self.rdtype)
         dudy = np.empty((2, n0 - 1, n1), dtype=self.rdtype)
         wnorm = np.empty((n0, n1), dtype=self.rdtype)
-        check(self.lib.gpa_extract_gradients(self.handle, _ptr(image), _ptr(kvecs), P, _ptr(klists), klists.shape[1],
+        check(self.lib.gpa_extract_gradients(self.handle, _ptr(image), _ptr(kvecs), P, _ptr(klists), K,
                                              float(sigma), int(mask_border), _ptr(dudx), _ptr(dudy), _ptr(wnorm)),
               'gpa_extract_gradients')
         return dudx, dudy, wnorm
@@ -695,12 +707,10 @@ class Plan:
     def tile_gradients_dev(self, image_ptr, image_pitch, r0, c0, mean, kvecs, klists, sigma, mask_border,
                            interior, dx, dy, wn):
         """interior = (i0, j0, t0, t1); dx, dy = (ptr, pitch, plane), wn = (ptr, pitch); element units."""
-        kvecs = _f64(kvecs).reshape(-1, 2)
-        P = len(kvecs)
-        klists = _f64(klists).reshape(P, -1, 2)
+        kvecs, P, klists, K = _peak_lists(kvecs, klists)
         i0, j0, t0, t1 = (int(v) for v in interior)
         check(self.lib.gpa_tile_gradients_dev(self.handle, _ptr(int(image_ptr)), int(image_pitch), int(r0), int(c0),
-                                              float(mean), _ptr(kvecs), P, _ptr(klists), klists.shape[1], float(sigma),
+                                              float(mean), _ptr(kvecs), P, _ptr(klists), K, float(sigma),
                                               int(mask_border), i0, j0, t0, t1, _ptr(int(dx[0])), int(dx[1]), int(dx[2]),
                                               _ptr(int(dy[0])), int(dy[1]), int(dy[2]), _ptr(int(wn[0])), int(wn[1])),
               'gpa_tile_gradients_dev')
@@ -717,12 +727,10 @@ class Plan:
     def tile_gradients_meandev_dev(self, image_ptr, image_pitch, r0, c0, kvecs, klists, sigma, mask_border, interior, dx, dy, wn):
         """tile_gradients_dev with the mean of gpa_tile_set_mean_dev; wn = (ptr, pitch, plane): plane != 0 writes the
         weight twice (plane elements apart)"""
-        kvecs = _f64(kvecs).reshape(-1, 2)
-        P = len(kvecs)
-        klists = _f64(klists).reshape(P, -1, 2)
+        kvecs, P, klists, K = _peak_lists(kvecs, klists)
         i0, j0, t0, t1 = (int(v) for v in interior)
         check(self.lib.gpa_tile_gradients_meandev_dev(self.handle, _ptr(int(image_ptr)), int(image_pitch), int(r0), int(c0),
-                                                      _ptr(kvecs), P, _ptr(klists), klists.shape[1], float(sigma),
+                                                      _ptr(kvecs), P, _ptr(klists), K, float(sigma),
                                                       int(mask_border), i0, j0, t0, t1, _ptr(int(dx[0])), int(dx[1]), int(dx[2]),
                                                       _ptr(int(dy[0])), int(dy[1]), int(dy[2]), _ptr(int(wn[0])), int(wn[1]),
                                                       int(wn[2])),
@@ -754,7 +762,7 @@ class Plan:
     def unwrap_prediff_dev(self, dx_ptr, dy_ptr, weight_ptr, phi_ptr, kmax=100, eps=1e-9, axes_compat=True):
         iters = C.c_int(0)
         check(self.lib.gpa_unwrap_prediff_dev(self.handle, _ptr(int(dx_ptr)), _ptr(int(dy_ptr)),
-                                              _ptr(None if weight_ptr is None else int(weight_ptr)), int(kmax), float(eps),
+                                              _ptr(weight_ptr), int(kmax), float(eps),
                                               int(bool(axes_compat)), _ptr(int(phi_ptr)), C.byref(iters)),
               'gpa_unwrap_prediff_dev')
         return iters.value
@@ -762,7 +770,7 @@ class Plan:
     def unwrap_prediff_enqueue_dev(self, dx_ptr, dy_ptr, weight_ptr, phi_ptr, kmax=100, eps=1e-9, axes_compat=True):
         """the solve of unwrap_prediff_dev put on the plan's stream without waiting for it (unwrap_finish does)"""
         check(self.lib.gpa_unwrap_prediff_enqueue_dev(self.handle, _ptr(int(dx_ptr)), _ptr(int(dy_ptr)),
-                                                      _ptr(None if weight_ptr is None else int(weight_ptr)), int(kmax),
+                                                      _ptr(weight_ptr), int(kmax),
                                                       float(eps), int(bool(axes_compat)), _ptr(int(phi_ptr))),
               'gpa_unwrap_prediff_enqueue_dev')
 
@@ -775,52 +783,26 @@ class Plan:
                                        lockins_ptr=None, kidx_ptr=None, grads_ptr=None, weights_ptr=None, grad_mode=0):
         """device pointers; grads_ptr (P x n0 x n1 x 2) / weights_ptr (P x n0 x n1): the winners' phase gradients and
         |lockins| from the same sweep (gpa_extract_displacement_field_grad_dev); without them the plain driver is called"""
-        kvecs = _f64(kvecs).reshape(-1, 2)
-        P = len(kvecs)
-        klists = _f64(klists).reshape(P, -1, 2)
         iters = (C.c_int * 2)()
-        if grads_ptr is not None or weights_ptr is not None:
-            check(self.lib.gpa_extract_displacement_field_grad_dev(self.handle, _ptr(image_ptr), _ptr(kvecs), P, _ptr(klists),
-                                                                   klists.shape[1], float(sigma), int(mask_border), int(kmax),
-                                                                   int(grad_mode), _ptr(u_ptr), _ptr(lockins_ptr), _ptr(kidx_ptr),
-                                                                   _ptr(grads_ptr), _ptr(weights_ptr), iters),
-                  'gpa_extract_displacement_field_grad_dev')
-            return iters[0], iters[1]
-        check(self.lib.gpa_extract_displacement_field_dev(self.handle, _ptr(image_ptr), _ptr(kvecs), P, _ptr(klists),
-                                                          klists.shape[1], float(sigma), int(mask_border), int(kmax),
-                                                          _ptr(u_ptr), _ptr(lockins_ptr), _ptr(kidx_ptr), iters),
-              'gpa_extract_displacement_field_dev')
+        self._extract_call('_dev', image_ptr, _peak_lists(kvecs, klists), sigma, mask_border, kmax, u_ptr, lockins_ptr, kidx_ptr,
+                           grads_ptr, weights_ptr, grad_mode, iters)
         return iters[0], iters[1]
 
     def extract_displacement_field_async(self, image_ptr, kvecs, klists, sigma, mask_border, kmax, u_ptr,
                                          lockins_ptr=None, kidx_ptr=None, grads_ptr=None, weights_ptr=None, grad_mode=0):
         """enqueue only; pair with sync() / last_iters()"""
-        kvecs = _f64(kvecs).reshape(-1, 2)
-        P = len(kvecs)
-        klists = _f64(klists).reshape(P, -1, 2)
-        if grads_ptr is not None or weights_ptr is not None:
-            check(self.lib.gpa_extract_displacement_field_grad_async(self.handle, _ptr(image_ptr), _ptr(kvecs), P, _ptr(klists),
-                                                                     klists.shape[1], float(sigma), int(mask_border), int(kmax),
-                                                                     int(grad_mode), _ptr(u_ptr), _ptr(lockins_ptr),
-                                                                     _ptr(kidx_ptr), _ptr(grads_ptr), _ptr(weights_ptr)),
-                  'gpa_extract_displacement_field_grad_async')
-            return
-        check(self.lib.gpa_extract_displacement_field_async(self.handle, _ptr(image_ptr), _ptr(kvecs), P, _ptr(klists),
-                                                            klists.shape[1], float(sigma), int(mask_border), int(kmax),
-                                                            _ptr(u_ptr), _ptr(lockins_ptr), _ptr(kidx_ptr)),
-              'gpa_extract_displacement_field_async')
+        self._extract_call('_async', image_ptr, _peak_lists(kvecs, klists), sigma, mask_border, kmax, u_ptr, lockins_ptr,
+                           kidx_ptr, grads_ptr, weights_ptr, grad_mode)
 
     def extract_displacement_field_batch_dev(self, images_ptr, nimages, kvecs, klists, sigma, mask_border, kmax, u_ptr,
                                              want_iters=True):
         """a stack of `nimages` images (device pointers: images nimages x n0 x n1, u nimages x 2 x n0 x n1): sweeps
         image after image, the 2 * nimages unwraps in one set of launches.  Returns the (nimages, 2) iteration counts,
         or None without synchronising when want_iters is False (pair with sync())"""
-        kvecs = _f64(kvecs).reshape(-1, 2)
-        P = len(kvecs)
-        klists = _f64(klists).reshape(P, -1, 2)
+        kvecs, P, klists, K = _peak_lists(kvecs, klists)
         it = (C.c_int * (2 * int(nimages)))() if want_iters else None
         check(self.lib.gpa_extract_displacement_field_batch_dev(self.handle, _ptr(images_ptr), int(nimages), _ptr(kvecs), P,
-                                                                _ptr(klists), klists.shape[1], float(sigma), int(mask_border),
+                                                                _ptr(klists), K, float(sigma), int(mask_border),
                                                                 int(kmax), _ptr(u_ptr), it),
               'gpa_extract_displacement_field_batch_dev')
         return None if it is None else np.array(it[:], dtype=np.int64).reshape(int(nimages), 2)

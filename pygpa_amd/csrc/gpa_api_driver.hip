@@ -3,19 +3,28 @@
 #include "gpa_plan.h"
 
 // ---- fused driver --------------------------------------------------------------
+// the optional outputs of a driver call (each may be NULL; grad_mode: the stencil of grads).  grads (P x n0 x n1 x 2) / absw
+// (P x n0 x n1) != NULL is the one-sweep form, see extract_launch
+struct ExtractOut {
+  void* lockins;
+  int32_t* kidx;
+  void* grads;
+  void* absw;
+  int grad_mode;
+};
+
+// the ranges every driver accepts, in the words of entry point `fn`
+static int check_ranges(gpa_plan* p, const std::string& fn, int P, int K, int kmax) {
+  if (P < 2 || P > p->max_peaks) return fail(GPA_ERR_STATE, fn + ": need 2 <= P <= 8");
+  if (K < 1 || P * K > p->max_batch) return fail(GPA_ERR_STATE, fn + ": P*K exceeds max_batch");
+  if (kmax < 1) return fail(GPA_ERR_ARG, "kmax must be >= 1");
+  return GPA_OK;
+}
+
 // host-side preparation: filter / carrier / k-matrix tables (re-staged only when they change; these upload
 // synchronously), the x-plane buffer, and the second unwrap workspace + stream
-int extract_stage(gpa_plan* p, const double* kvecs, int P, const double* klists, int K, double sigma, int* Bx) {
-  const int B = P * K;
-  TRY(ensure_filters(p, sigma));
-  std::vector<double> kr((size_t)B * 2);
-  for (int pp = 0; pp < P; ++pp)
-    for (int k = 0; k < K; ++k) {
-      kr[2 * ((size_t)pp * K + k)] = kvecs[2 * pp];
-      kr[2 * ((size_t)pp * K + k) + 1] = kvecs[2 * pp + 1];
-    }
-  TRY(stage_kvectors(p, klists, kr.data(), B, Bx));
-  TRY(ensure_tbuf(p, *Bx));
+static int extract_stage(gpa_plan* p, const double* kvecs, int P, const double* klists, int K, double sigma, int* Bx) {
+  TRY(stage_sweep(p, kvecs, P, klists, K, sigma, Bx));
   TRY(stage_kmat(p, kvecs, P));
   {
     // (PAIR_MAXSIDE: measurement switch for the size up to which both components share one set of launches)
@@ -48,26 +57,29 @@ int extract_stage(gpa_plan* p, const double* kvecs, int P, const double* klists,
 }
 
 // every launch of the driver, nothing else: this is what a hipGraph of the call holds
-// grads (P x n0 x n1 x 2) / absw (P x n0 x n1) != NULL: the one-sweep form -- pass B also leaves the phase of every candidate in
-// p->d_sf (sized by the caller), the multi-peak stencil turns them into the winners' phase gradients, |lock-in| goes to absw;
-// the lock-ins are compensated then, kidx is not NULL.  Both NULL: the launches of the plain driver, nothing else.
-int extract_launch(gpa_plan* p, const void* image, int P, int K, int Bx, int mask_border, int kmax, void* u,
-                          void* lk, int32_t* kidx, bool want_lockins, void* grads, void* absw, int grad_mode) {
+// o.grads / o.absw != NULL: the one-sweep form -- pass B also leaves the phase of every candidate in p->d_sf (sized by the
+// caller), the multi-peak stencil turns them into the winners' phase gradients, |lock-in| goes to absw; the lock-ins are
+// compensated then.  Both NULL: the launches of the plain driver, nothing else.
+static int extract_launch(gpa_plan* p, const void* image, int P, int K, int Bx, int mask_border, int kmax, void* u,
+                          const ExtractOut& o) {
   const size_t npx = (size_t)p->n0 * p->n1;
+  void* lk = o.lockins ? o.lockins : p->d_lockin;
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[0], p->stream));
   HIP_TRY(launch_mean(p->dtype, image, npx, p->d_scratch, p->d_mean, p->stream));
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[1], p->stream));
-  TRY(run_passA(p, image, p->d_mean, p->Tbuf, Bx));
+  TRY(run_passA(p, image, p->d_mean, p->Tbuf, Bx, 1));
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[2], p->stream));
-  if (grads) {
+  if (o.grads) {
+    int32_t* kidx = o.kidx ? o.kidx : p->d_kidx;   // (the stencil reads the winners' indices)
     bool shared = false;
     TRY(passB_phases(p, P, K, lk, kidx, p->d_sf, &shared));
-    HIP_TRY(launch_phasegrad(p->dtype, p->d_sf, K, kidx, p->n0, p->n1, p->d_kl, p->d_kr, grad_mode, grads, p->stream,
+    HIP_TRY(launch_phasegrad(p->dtype, p->d_sf, K, kidx, p->n0, p->n1, p->d_kl, p->d_kr, o.grad_mode, o.grads, p->stream,
                              shared ? p->d_ystep : nullptr, P));
   } else {
-    TRY(passB_select(p, P, K, lk, kidx, !want_lockins && !absw));
+    // (lock-ins nobody reads but reconstruct_setup may stay raw)
+    TRY(passB_select(p, {p->Tbuf, 1, 0}, P, K, lk, o.kidx, !o.lockins && !o.absw));
   }
-  if (absw) HIP_TRY(launch_cabs(p->dtype, lk, (size_t)P * npx, absw, p->stream));
+  if (o.absw) HIP_TRY(launch_cabs(p->dtype, lk, (size_t)P * npx, o.absw, p->stream));
   const double* ystep = p->lk_raw ? p->d_ystep : nullptr;
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[3], p->stream));
   // phases / weights / per-pixel least squares fused with the unwrap's set-up: the gradient fields never
@@ -128,41 +140,184 @@ int extract_launch(gpa_plan* p, const void* image, int P, int K, int Bx, int mas
 // (Rounds 2-4 could capture them into a hipGraph -- USE_GRAPH=1 -- and replay it: measured NOT faster than eager launches at
 // any size on MI355X / ROCm 7.2, 512^2 0.65 against 0.60 ms, 4096^2 equal, and it serialised with the copy stream of
 // gpa_download_async: profiles/r02_graph_vs_eager.txt.  Removed in round 5; git history has it.)
-// what: the entry point's name for the messages.  grads / absw (nullable): the one-sweep form, see extract_launch
-int extract_enqueue(gpa_plan* p, const void* image, const double* kvecs, int P, const double* klists, int K,
-                           double sigma, int mask_border, int kmax, void* u, void* lockins, int32_t* kidx, void* grads,
-                           void* absw, int grad_mode, const char* what) {
+// what: the entry point's name for the messages
+static int extract_enqueue(gpa_plan* p, const char* what, const void* image, const double* kvecs, int P, const double* klists,
+                           int K, double sigma, int mask_border, int kmax, void* u, const ExtractOut& o) {
   const std::string fn(what);
   if (!p || !image || !kvecs || !klists || !u) return fail(GPA_ERR_ARG, fn + ": null argument");
-  if (P < 2 || P > p->max_peaks) return fail(GPA_ERR_STATE, fn + ": need 2 <= P <= 8");
-  if (K < 1 || P * K > p->max_batch) return fail(GPA_ERR_STATE, fn + ": P*K exceeds max_batch");
-  if (kmax < 1) return fail(GPA_ERR_ARG, "kmax must be >= 1");
-  if (grads && (grad_mode < 0 || grad_mode > 2)) return fail(GPA_ERR_ARG, fn + ": grad_mode must be 0, 1 or 2");
+  TRY(check_ranges(p, fn, P, K, kmax));
+  if (o.grads && (o.grad_mode < 0 || o.grad_mode > 2)) return fail(GPA_ERR_ARG, fn + ": grad_mode must be 0, 1 or 2");
   HIP_TRY(hipSetDevice(p->device));
   int Bx = 0;
   TRY(extract_stage(p, kvecs, P, klists, K, sigma, &Bx));
-  void* lk = lockins ? lockins : p->d_lockin;
-  if (grads) {
-    // the phases of all P K candidates (reals): allocated by the first call that asks for gradients, kept by the plan
-    TRY(ensure_sf(p, (size_t)P * K * p->n0 * p->n1 * p->rsz));
-    if (!kidx) kidx = p->d_kidx;
-  }
+  // the phases of all P K candidates (reals): allocated by the first call that asks for gradients, kept by the plan
+  if (o.grads) TRY(ensure_sf(p, (size_t)P * K * p->n0 * p->n1 * p->rsz));
   // per-kernel event pairs while profiling (installed for this thread until the function returns)
   ProfInstall prof(p);
-  return extract_launch(p, image, P, K, Bx, mask_border, kmax, u, lk, kidx, lockins != nullptr, grads, absw, grad_mode);
+  return extract_launch(p, image, P, K, Bx, mask_border, kmax, u, o);
+}
+
+// the iteration counts of the last driver call, once its stream has been waited for
+static void read_iters(const gpa_plan* p, int* iters2) {
+  iters2[0] = p->h_iters[p->iters_off];
+  iters2[1] = p->h_iters[p->iters_stride + p->iters_off];
+}
+
+int gpa_last_iters(gpa_plan* p, int* iters2) {
+  if (!p || !iters2) return fail(GPA_ERR_ARG, "null argument");
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  read_iters(p, iters2);
+  return GPA_OK;
+}
+
+// the synchronising end of a driver call: stage / kernel times of a profiled call, iteration counts
+static int extract_finish(gpa_plan* p, int* iters_out) {
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  if (p->profiling) {
+    for (int i = 0; i < 5; ++i) hipEventElapsedTime(&p->stage_ms[i], p->stage_ev[i], p->stage_ev[i + 1]);
+    collect_kernel_profile(p);
+  }
+  if (iters_out) read_iters(p, iters_out);
+  return GPA_OK;
+}
+
+// the host-pointer form: upload, enqueue on the plan's staging buffers, finish, download what was asked for (o: host pointers)
+static int extract_host(gpa_plan* p, const char* what, const void* image, const double* kvecs, int P, const double* klists,
+                        int K, double sigma, int mask_border, int kmax, void* u, const ExtractOut& o, int* iters_out) {
+  if (!p || !image || !u) return fail(GPA_ERR_ARG, std::string(what) + ": null argument");
+  HIP_TRY(hipSetDevice(p->device));
+  const size_t npx = (size_t)p->n0 * p->n1;
+  // device staging of the one-sweep outputs, sized for the plan's peaks on the first call that asks for them
+  if (o.grads && !p->d_grads) TRY(dmalloc(p, &p->d_grads, (size_t)p->max_peaks * 2 * npx * p->rsz));
+  if (o.absw && !p->d_absw) TRY(dmalloc(p, &p->d_absw, (size_t)p->max_peaks * npx * p->rsz));
+  HIP_TRY(hipMemcpyAsync(p->d_image, image, npx * p->rsz, hipMemcpyHostToDevice, p->stream));
+  const ExtractOut dev{o.lockins ? p->d_lockin : nullptr, o.kidx ? p->d_kidx : nullptr, o.grads ? p->d_grads : nullptr,
+                       o.absw ? p->d_absw : nullptr, o.grad_mode};
+  TRY(extract_enqueue(p, what, p->d_image, kvecs, P, klists, K, sigma, mask_border, kmax, p->d_u, dev));
+  TRY(extract_finish(p, iters_out));
+  HIP_TRY(hipMemcpyAsync(u, p->d_u, 2 * npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
+  if (o.lockins) HIP_TRY(hipMemcpyAsync(o.lockins, p->d_lockin, (size_t)P * npx * p->csz, hipMemcpyDeviceToHost, p->stream));
+  if (o.kidx) HIP_TRY(hipMemcpyAsync(o.kidx, p->d_kidx, (size_t)P * npx * sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
+  if (o.grads) HIP_TRY(hipMemcpyAsync(o.grads, p->d_grads, (size_t)P * 2 * npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
+  if (o.absw) HIP_TRY(hipMemcpyAsync(o.absw, p->d_absw, (size_t)P * npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return GPA_OK;
+}
+
+// ---- the entry points: host pointers / device pointers / enqueue only, each plain (messages in the name of
+// gpa_extract_displacement_field) and with the one-sweep outputs (messages in the entry point's own name)
+int gpa_extract_displacement_field(gpa_plan* p, const void* image, const double* kvecs, int P,
+                                   const double* klists, int K, double sigma, int mask_border, int kmax,
+                                   void* u, void* lockins, int32_t* kidx, int* iters_out) {
+  return extract_host(p, "gpa_extract_displacement_field", image, kvecs, P, klists, K, sigma, mask_border, kmax, u,
+                      {lockins, kidx, nullptr, nullptr, 0}, iters_out);
+}
+
+int gpa_extract_displacement_field_grad(gpa_plan* p, const void* image, const double* kvecs, int P,
+                                        const double* klists, int K, double sigma, int mask_border, int kmax,
+                                        int grad_mode, void* u, void* lockins, int32_t* kidx, void* grads, void* absw,
+                                        int* iters_out) {
+  return extract_host(p, "gpa_extract_displacement_field_grad", image, kvecs, P, klists, K, sigma, mask_border, kmax, u,
+                      {lockins, kidx, grads, absw, grad_mode}, iters_out);
+}
+
+int gpa_extract_displacement_field_dev(gpa_plan* p, const void* image, const double* kvecs, int P,
+                                       const double* klists, int K, double sigma, int mask_border, int kmax,
+                                       void* u, void* lockins, int32_t* kidx, int* iters_out) {
+  TRY(extract_enqueue(p, "gpa_extract_displacement_field", image, kvecs, P, klists, K, sigma, mask_border, kmax, u,
+                      {lockins, kidx, nullptr, nullptr, 0}));
+  return extract_finish(p, iters_out);
+}
+
+int gpa_extract_displacement_field_grad_dev(gpa_plan* p, const void* image, const double* kvecs, int P,
+                                            const double* klists, int K, double sigma, int mask_border, int kmax,
+                                            int grad_mode, void* u, void* lockins, int32_t* kidx, void* grads, void* absw,
+                                            int* iters_out) {
+  TRY(extract_enqueue(p, "gpa_extract_displacement_field_grad_dev", image, kvecs, P, klists, K, sigma, mask_border, kmax, u,
+                      {lockins, kidx, grads, absw, grad_mode}));
+  return extract_finish(p, iters_out);
 }
 
 int gpa_extract_displacement_field_async(gpa_plan* p, const void* image, const double* kvecs, int P,
                                          const double* klists, int K, double sigma, int mask_border, int kmax,
                                          void* u, void* lockins, int32_t* kidx) {
-  return extract_enqueue(p, image, kvecs, P, klists, K, sigma, mask_border, kmax, u, lockins, kidx);
+  return extract_enqueue(p, "gpa_extract_displacement_field", image, kvecs, P, klists, K, sigma, mask_border, kmax, u,
+                         {lockins, kidx, nullptr, nullptr, 0});
 }
 
 int gpa_extract_displacement_field_grad_async(gpa_plan* p, const void* image, const double* kvecs, int P,
                                               const double* klists, int K, double sigma, int mask_border, int kmax,
                                               int grad_mode, void* u, void* lockins, int32_t* kidx, void* grads, void* absw) {
-  return extract_enqueue(p, image, kvecs, P, klists, K, sigma, mask_border, kmax, u, lockins, kidx, grads, absw, grad_mode,
-                         "gpa_extract_displacement_field_grad_async");
+  return extract_enqueue(p, "gpa_extract_displacement_field_grad_async", image, kvecs, P, klists, K, sigma, mask_border, kmax, u,
+                         {lockins, kidx, grads, absw, grad_mode});
+}
+
+// ---- batched driver ---------------------------------------------------------------
+// the unwrap workspace of the 2 B problems of B images, their weights and pinned iteration counts.  It is a capacity: fewer
+// frames (a ragged last chunk, a shorter stack) reuse it
+static int ensure_batch_unwrap(gpa_plan* p, int B) {
+  if (B <= p->uwb_images) {
+    if (!unwrap_set_active(&p->uwb, 2 * B)) return fail(GPA_ERR_STATE, "batched unwrap workspace: bad active count");
+    return GPA_OK;
+  }
+  const size_t npx = (size_t)p->n0 * p->n1;
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  if (p->uwb_images) {
+    unwrap_workspace_destroy(&p->uwb);
+    (void)hipFree(p->d_wnorm_b);
+    (void)hipHostFree(p->h_iters_b);
+    p->uwb_images = 0;
+    p->d_wnorm_b = nullptr;
+    p->h_iters_b = nullptr;
+  }
+  size_t bb = 0;
+  hipError_t e = unwrap_workspace_create(p->dtype, p->n0, p->n1, p->stream, &p->uwb, &bb, 2 * B);
+  if (e != hipSuccess) {
+    unwrap_workspace_destroy(&p->uwb);
+    return fail(GPA_ERR_HIP, std::string("batched unwrap workspace: ") + hipGetErrorString(e));
+  }
+  if (!unwrap_supports_batch(&p->uwb)) {
+    unwrap_workspace_destroy(&p->uwb);
+    return fail(GPA_ERR_STATE, "gpa_extract_displacement_field_batch: this image shape has no batched unwrap");
+  }
+  e = hipMalloc(&p->d_wnorm_b, (size_t)B * npx * p->rsz);
+  if (e == hipSuccess) e = hipHostMalloc((void**)&p->h_iters_b, (size_t)8 * B * sizeof(int));
+  if (e != hipSuccess) {
+    unwrap_workspace_destroy(&p->uwb);
+    if (p->d_wnorm_b) (void)hipFree(p->d_wnorm_b);
+    p->d_wnorm_b = nullptr;
+    return fail(GPA_ERR_HIP, std::string("batched driver buffers: ") + hipGetErrorString(e));
+  }
+  p->uwb_images = B;
+  return GPA_OK;
+}
+
+// x-planes (t_img bytes per image), lock-ins (l_img), means and mean scratch of a chunk of images swept in one set of launches
+static int ensure_batch_sweep(gpa_plan* p, int chunk, size_t t_img, size_t l_img) {
+  if ((size_t)chunk * t_img <= p->bT_bytes && (size_t)chunk * l_img <= p->bL_bytes && chunk <= p->b_chunk) return GPA_OK;
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  for (void* b : {p->bT, p->bL, p->bMean, (void*)p->bScratch})
+    if (b) (void)hipFree(b);
+  p->bT = p->bL = p->bMean = nullptr;
+  p->bScratch = nullptr;
+  p->bT_bytes = p->bL_bytes = 0;
+  p->b_chunk = 0;
+  hipError_t ea = hipMalloc(&p->bT, (size_t)chunk * t_img);
+  if (ea == hipSuccess) ea = hipMalloc(&p->bL, (size_t)chunk * l_img);
+  if (ea == hipSuccess) ea = hipMalloc(&p->bMean, (size_t)chunk * 8);
+  if (ea == hipSuccess) ea = hipMalloc((void**)&p->bScratch, (size_t)chunk * 1024 * sizeof(double));
+  if (ea != hipSuccess) return fail(GPA_ERR_HIP, std::string("batched sweep buffers: ") + hipGetErrorString(ea));
+  p->bT_bytes = (size_t)chunk * t_img;
+  p->bL_bytes = (size_t)chunk * l_img;
+  p->b_chunk = chunk;
+  return GPA_OK;
+}
+
+// the iteration counts of the last batched call (2 per image), after waiting for it
+static int read_batch_iters(gpa_plan* p, int B, int* iters_out) {
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  for (int j = 0; j < 2 * B; ++j) iters_out[j] = p->h_iters_b[4 * j + unwrap_iters_slot(&p->uwb)];
+  return GPA_OK;
 }
 
 // A stack of images of one shape in one call: every kernel of the driver takes an image / problem index from its
@@ -173,70 +328,20 @@ int gpa_extract_displacement_field_grad_async(gpa_plan* p, const void* image, co
 int gpa_extract_displacement_field_batch_dev(gpa_plan* p, const void* images, int B, const double* kvecs, int P,
                                              const double* klists, int K, double sigma, int mask_border, int kmax,
                                              void* u, int* iters_out) {
-  if (!p || !images || !kvecs || !klists || !u) return fail(GPA_ERR_ARG, "gpa_extract_displacement_field_batch: null argument");
-  if (B < 1 || B > 4096) return fail(GPA_ERR_ARG, "gpa_extract_displacement_field_batch: need 1 <= images <= 4096");
-  if (P < 2 || P > p->max_peaks) return fail(GPA_ERR_STATE, "gpa_extract_displacement_field_batch: need 2 <= P <= 8");
-  if (K < 1 || P * K > p->max_batch) return fail(GPA_ERR_STATE, "gpa_extract_displacement_field_batch: P*K exceeds max_batch");
-  if (kmax < 1) return fail(GPA_ERR_ARG, "kmax must be >= 1");
+  const char* fn = "gpa_extract_displacement_field_batch";
+  if (!p || !images || !kvecs || !klists || !u) return fail(GPA_ERR_ARG, std::string(fn) + ": null argument");
+  if (B < 1 || B > 4096) return fail(GPA_ERR_ARG, std::string(fn) + ": need 1 <= images <= 4096");
+  TRY(check_ranges(p, fn, P, K, kmax));
   HIP_TRY(hipSetDevice(p->device));
   int Bx = 0;
   TRY(extract_stage(p, kvecs, P, klists, K, sigma, &Bx));
+  TRY(ensure_batch_unwrap(p, B));
   const size_t npx = (size_t)p->n0 * p->n1;
-  // the batched workspace is a capacity: fewer frames (a ragged last chunk, a shorter stack) reuse it
-  if (B <= p->uwb_images) {
-    if (!unwrap_set_active(&p->uwb, 2 * B)) return fail(GPA_ERR_STATE, "batched unwrap workspace: bad active count");
-  } else {
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (p->uwb_images) {
-      unwrap_workspace_destroy(&p->uwb);
-      (void)hipFree(p->d_wnorm_b);
-      (void)hipHostFree(p->h_iters_b);
-      p->uwb_images = 0;
-      p->d_wnorm_b = nullptr;
-      p->h_iters_b = nullptr;
-    }
-    size_t bb = 0;
-    hipError_t e = unwrap_workspace_create(p->dtype, p->n0, p->n1, p->stream, &p->uwb, &bb, 2 * B);
-    if (e != hipSuccess) {
-      unwrap_workspace_destroy(&p->uwb);
-      return fail(GPA_ERR_HIP, std::string("batched unwrap workspace: ") + hipGetErrorString(e));
-    }
-    if (!unwrap_supports_batch(&p->uwb)) {
-      unwrap_workspace_destroy(&p->uwb);
-      return fail(GPA_ERR_STATE, "gpa_extract_displacement_field_batch: this image shape has no batched unwrap");
-    }
-    e = hipMalloc(&p->d_wnorm_b, (size_t)B * npx * p->rsz);
-    if (e == hipSuccess) e = hipHostMalloc((void**)&p->h_iters_b, (size_t)8 * B * sizeof(int));
-    if (e != hipSuccess) {
-      unwrap_workspace_destroy(&p->uwb);
-      if (p->d_wnorm_b) (void)hipFree(p->d_wnorm_b);
-      p->d_wnorm_b = nullptr;
-      return fail(GPA_ERR_HIP, std::string("batched driver buffers: ") + hipGetErrorString(e));
-    }
-    p->uwb_images = B;
-  }
   // the sweep and the least squares of a chunk of images are ONE set of launches too (blockIdx.z / .y = image);
   // the chunk is what fits ~3 GB of x-planes (512^2: the whole stack, 4096^2: one image at a time)
   const size_t t_img = (size_t)Bx * npx * p->csz, l_img = (size_t)P * npx * p->csz;
-  int chunk = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, ((size_t)3 << 30) / t_img));
-  if ((size_t)chunk * t_img > p->bT_bytes || (size_t)chunk * l_img > p->bL_bytes || chunk > p->b_chunk) {
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    for (void* b : {p->bT, p->bL, p->bMean, (void*)p->bScratch})
-      if (b) (void)hipFree(b);
-    p->bT = p->bL = p->bMean = nullptr;
-    p->bScratch = nullptr;
-    p->bT_bytes = p->bL_bytes = 0;
-    p->b_chunk = 0;
-    hipError_t ea = hipMalloc(&p->bT, (size_t)chunk * t_img);
-    if (ea == hipSuccess) ea = hipMalloc(&p->bL, (size_t)chunk * l_img);
-    if (ea == hipSuccess) ea = hipMalloc(&p->bMean, (size_t)chunk * 8);
-    if (ea == hipSuccess) ea = hipMalloc((void**)&p->bScratch, (size_t)chunk * 1024 * sizeof(double));
-    if (ea != hipSuccess) return fail(GPA_ERR_HIP, std::string("batched sweep buffers: ") + hipGetErrorString(ea));
-    p->bT_bytes = (size_t)chunk * t_img;
-    p->bL_bytes = (size_t)chunk * l_img;
-    p->b_chunk = chunk;
-  }
-  TRY(shared_prepare(p, P, K));
+  const int chunk = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, ((size_t)3 << 30) / t_img));
+  TRY(ensure_batch_sweep(p, chunk, t_img, l_img));
   int nparts = 0;
   const size_t rstride = 2 * npx;                                                     // residual slices per image
   const size_t pstride = (size_t)(unwrap_partials_buffer(&p->uwb, 2) - unwrap_partials_buffer(&p->uwb, 0));
@@ -245,28 +350,17 @@ int gpa_extract_displacement_field_batch_dev(gpa_plan* p, const void* images, in
     const void* image = (const char*)images + (size_t)c0 * npx * p->rsz;
     HIP_TRY(launch_mean(p->dtype, image, npx, p->bScratch, p->bMean, p->stream, nimg));
     TRY(run_passA(p, image, p->bMean, p->bT, Bx, nimg));
-    const bool raw = p->sh_use && !opt_set(OPT_NO_RAW);   // (the stack's lock-ins are never handed out)
-    if (p->sh_use)
-      HIP_TRY(launch_passB_shared(p->dtype, p->ax1s, p->n0, p->bT, p->ax1s.L == p->ax1.L ? p->tw1 : p->tw1s, p->tb,
-                                  p->sh, p->sh_E, p->sh_Epad, P, K, p->bL, nullptr, p->stream, nimg, Bx, p->sh_elems, p->sh_nbl,
-                                  raw));
-    else
-      HIP_TRY(launch_passB(p->dtype, p->ax1, p->n0, p->bT, p->Hy, p->tw1, p->tb, P, K, true, p->bL, nullptr, p->stream, nimg,
-                           Bx));
+    TRY(passB_select(p, {p->bT, nimg, Bx}, P, K, p->bL, nullptr, true));   // (the stack's lock-ins are never handed out)
     HIP_TRY(launch_reconstruct_setup(p->dtype, p->bL, p->d_kmat, P, p->n0, p->n1, mask_border,
                                      (char*)p->d_wnorm_b + (size_t)c0 * npx * p->rsz,
                                      unwrap_residual_buffer(&p->uwb, 2 * c0), unwrap_residual_buffer(&p->uwb, 2 * c0 + 1),
                                      unwrap_partials_buffer(&p->uwb, 2 * c0), unwrap_partials_buffer(&p->uwb, 2 * c0 + 1),
-                                     &nparts, p->stream, nimg, rstride, pstride, raw ? p->d_ystep : nullptr));
+                                     &nparts, p->stream, nimg, rstride, pstride, p->lk_raw ? p->d_ystep : nullptr));
   }
   hipError_t e = unwrap_enqueue_prepared(&p->uwb, p->d_wnorm_b, nparts, kmax, 1e-9, true, u, p->stream);
   if (e == hipSuccess) e = unwrap_fetch_iters(&p->uwb, p->h_iters_b, p->stream);
   if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("batched unwrap: ") + hipGetErrorString(e));
-  if (iters_out) {
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    for (int j = 0; j < 2 * B; ++j) iters_out[j] = p->h_iters_b[4 * j + unwrap_iters_slot(&p->uwb)];
-  }
-  return GPA_OK;
+  return iters_out ? read_batch_iters(p, B, iters_out) : GPA_OK;
 }
 
 // whether gpa_extract_displacement_field_batch_dev can take this plan's image shape (the fused iteration covers it);
@@ -278,93 +372,14 @@ int gpa_supports_batch(gpa_plan* p) {
 
 int gpa_last_batch_iters(gpa_plan* p, int B, int* iters_out) {
   if (!p || !iters_out || B < 1 || B > p->uwb_images) return fail(GPA_ERR_ARG, "gpa_last_batch_iters: bad argument");
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  for (int j = 0; j < 2 * B; ++j) iters_out[j] = p->h_iters_b[4 * j + unwrap_iters_slot(&p->uwb)];
-  return GPA_OK;
-}
-
-int gpa_last_iters(gpa_plan* p, int* iters2) {
-  if (!p || !iters2) return fail(GPA_ERR_ARG, "null argument");
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  iters2[0] = p->h_iters[p->iters_off];
-  iters2[1] = p->h_iters[p->iters_stride + p->iters_off];
-  return GPA_OK;
-}
-
-// the synchronising end of a driver call: stage / kernel times of a profiled call, iteration counts
-static int extract_finish(gpa_plan* p, int* iters_out) {
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  if (p->profiling) {
-    for (int i = 0; i < 5; ++i) hipEventElapsedTime(&p->stage_ms[i], p->stage_ev[i], p->stage_ev[i + 1]);
-    collect_kernel_profile(p);
-  }
-  if (iters_out) { iters_out[0] = p->h_iters[p->iters_off]; iters_out[1] = p->h_iters[p->iters_stride + p->iters_off]; }
-  return GPA_OK;
-}
-
-int gpa_extract_displacement_field_dev(gpa_plan* p, const void* image, const double* kvecs, int P,
-                                       const double* klists, int K, double sigma, int mask_border, int kmax,
-                                       void* u, void* lockins, int32_t* kidx, int* iters_out) {
-  TRY(extract_enqueue(p, image, kvecs, P, klists, K, sigma, mask_border, kmax, u, lockins, kidx));
-  return extract_finish(p, iters_out);
-}
-
-int gpa_extract_displacement_field_grad_dev(gpa_plan* p, const void* image, const double* kvecs, int P,
-                                            const double* klists, int K, double sigma, int mask_border, int kmax,
-                                            int grad_mode, void* u, void* lockins, int32_t* kidx, void* grads, void* absw,
-                                            int* iters_out) {
-  TRY(extract_enqueue(p, image, kvecs, P, klists, K, sigma, mask_border, kmax, u, lockins, kidx, grads, absw, grad_mode,
-                      "gpa_extract_displacement_field_grad_dev"));
-  return extract_finish(p, iters_out);
-}
-
-int gpa_extract_displacement_field_grad(gpa_plan* p, const void* image, const double* kvecs, int P,
-                                        const double* klists, int K, double sigma, int mask_border, int kmax,
-                                        int grad_mode, void* u, void* lockins, int32_t* kidx, void* grads, void* absw,
-                                        int* iters_out) {
-  if (!p || !image || !u) return fail(GPA_ERR_ARG, "gpa_extract_displacement_field_grad: null argument");
-  if (P < 2 || P > p->max_peaks) return fail(GPA_ERR_STATE, "gpa_extract_displacement_field_grad: need 2 <= P <= 8");
-  HIP_TRY(hipSetDevice(p->device));
-  const size_t npx = (size_t)p->n0 * p->n1;
-  // device staging of the two new outputs, sized for the plan's peaks on the first call that asks for them
-  if (grads && !p->d_grads) TRY(dmalloc(p, &p->d_grads, (size_t)p->max_peaks * 2 * npx * p->rsz));
-  if (absw && !p->d_absw) TRY(dmalloc(p, &p->d_absw, (size_t)p->max_peaks * npx * p->rsz));
-  HIP_TRY(hipMemcpyAsync(p->d_image, image, npx * p->rsz, hipMemcpyHostToDevice, p->stream));
-  TRY(extract_enqueue(p, p->d_image, kvecs, P, klists, K, sigma, mask_border, kmax, p->d_u, lockins ? p->d_lockin : nullptr,
-                      kidx ? p->d_kidx : nullptr, grads ? p->d_grads : nullptr, absw ? p->d_absw : nullptr, grad_mode,
-                      "gpa_extract_displacement_field_grad"));
-  TRY(extract_finish(p, iters_out));
-  HIP_TRY(hipMemcpyAsync(u, p->d_u, 2 * npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
-  if (lockins) HIP_TRY(hipMemcpyAsync(lockins, p->d_lockin, (size_t)P * npx * p->csz, hipMemcpyDeviceToHost, p->stream));
-  if (kidx) HIP_TRY(hipMemcpyAsync(kidx, p->d_kidx, (size_t)P * npx * sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
-  if (grads) HIP_TRY(hipMemcpyAsync(grads, p->d_grads, (size_t)P * 2 * npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
-  if (absw) HIP_TRY(hipMemcpyAsync(absw, p->d_absw, (size_t)P * npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return GPA_OK;
-}
-
-int gpa_extract_displacement_field(gpa_plan* p, const void* image, const double* kvecs, int P,
-                                   const double* klists, int K, double sigma, int mask_border, int kmax,
-                                   void* u, void* lockins, int32_t* kidx, int* iters_out) {
-  if (!p || !image || !u) return fail(GPA_ERR_ARG, "gpa_extract_displacement_field: null argument");
-  HIP_TRY(hipSetDevice(p->device));
-  const size_t npx = (size_t)p->n0 * p->n1;
-  HIP_TRY(hipMemcpyAsync(p->d_image, image, npx * p->rsz, hipMemcpyHostToDevice, p->stream));
-  TRY(gpa_extract_displacement_field_dev(p, p->d_image, kvecs, P, klists, K, sigma, mask_border, kmax, p->d_u,
-                                         lockins ? p->d_lockin : nullptr, kidx ? p->d_kidx : nullptr, iters_out));
-  HIP_TRY(hipMemcpyAsync(u, p->d_u, 2 * npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
-  if (lockins) HIP_TRY(hipMemcpyAsync(lockins, p->d_lockin, (size_t)P * npx * p->csz, hipMemcpyDeviceToHost, p->stream));
-  if (kidx) HIP_TRY(hipMemcpyAsync(kidx, p->d_kidx, (size_t)P * npx * sizeof(int32_t), hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  return GPA_OK;
+  return read_batch_iters(p, B, iters_out);
 }
 
 int gpa_extract_gradients(gpa_plan* p, const void* image, const double* kvecs, int P, const double* klists, int K,
                           double sigma, int mask_border, void* dudx, void* dudy, void* wnorm) {
   if (!p || !image || !kvecs || !klists || !dudx || !dudy || !wnorm)
     return fail(GPA_ERR_ARG, "gpa_extract_gradients: null argument");
-  if (P < 2 || P > p->max_peaks) return fail(GPA_ERR_STATE, "gpa_extract_gradients: need 2 <= P <= 8");
-  if (K < 1 || P * K > p->max_batch) return fail(GPA_ERR_STATE, "gpa_extract_gradients: P*K exceeds max_batch");
+  TRY(check_ranges(p, "gpa_extract_gradients", P, K, 1));   // (no unwrap here: no kmax)
   HIP_TRY(hipSetDevice(p->device));
   const size_t npx = (size_t)p->n0 * p->n1;
   HIP_TRY(hipMemcpyAsync(p->d_image, image, npx * p->rsz, hipMemcpyHostToDevice, p->stream));

@@ -240,24 +240,16 @@ int stage_kvectors(gpa_plan* p, const double* kl, const double* kr_per_b, int B,
 int ensure_tbuf(gpa_plan* p, int planes);
 int ensure_sf(gpa_plan* p, size_t bytes);
 int stage_kmat(gpa_plan* p, const double* kvecs, int P);
-int run_passA(gpa_plan* p, const void* image, const void* mean, void* Tbuf, int Bx, int nimg = 1);
-int passB_select(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, bool raw = false);
+// the x-planes pass B reads: those of one image in the plan's own buffer ({p->Tbuf, 1, 0}), or those of a stack of nimg images
+// `stride` planes apart (stride != 0 marks a stack)
+struct XPlanes { const void* T; int nimg, stride; };
+int stage_sweep(gpa_plan* p, const double* krefs, int P, const double* klists, int K, double sigma, int* Bx);
+int run_passA(gpa_plan* p, const void* image, const void* mean, void* Tbuf, int Bx, int nimg);
+int passB_select(gpa_plan* p, const XPlanes& xp, int P, int K, void* lockin, int32_t* kidx, bool raw);
 int passB_phases(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, void* psi, bool* shared);
 void collect_kernel_profile(gpa_plan* p);
 int sweep_peaks_dev(gpa_plan* p, const void* image, const void* mean, const double* krefs, int P,
-                           const double* klists, int K, double sigma, void* lockin, int32_t* kidx, bool raw = false);
-int sweep_one_peak(gpa_plan* p, const void* image, const double* kref, const double* klist, int K, double sigma,
-                          int mode, void* lockin, int32_t* kidx, const uint8_t* d_gate, void* d_psi);
-int sweep_host(gpa_plan* p, const void* image, const double* kref, const double* klist, int K, double sigma,
-                      int grad_mode, const uint8_t* gate, void* lockin, int32_t* kidx, void* grad);
-int extract_stage(gpa_plan* p, const double* kvecs, int P, const double* klists, int K, double sigma, int* Bx);
-int extract_launch(gpa_plan* p, const void* image, int P, int K, int Bx, int mask_border, int kmax, void* u,
-                          void* lk, int32_t* kidx, bool want_lockins, void* grads = nullptr, void* absw = nullptr,
-                          int grad_mode = 0);
-int extract_enqueue(gpa_plan* p, const void* image, const double* kvecs, int P, const double* klists, int K,
-                           double sigma, int mask_border, int kmax, void* u, void* lockins, int32_t* kidx,
-                           void* grads = nullptr, void* absw = nullptr, int grad_mode = 0,
-                           const char* what = "gpa_extract_displacement_field");
+                           const double* klists, int K, double sigma, void* lockin, int32_t* kidx, bool raw);
 int tile_gradients_impl(gpa_plan* p, const void* image, size_t image_pitch, int r0, int c0, bool mean_on_device,
                                double mean, const double* kvecs, int P, const double* klists, int K, double sigma,
                                int mask_border, int i0, int j0, int t0, int t1, void* dx, size_t dx_pitch, size_t dx_plane,
