@@ -39,6 +39,13 @@ EXTRA_FLAGS = {'gpa_unwrap_rowhalf.hip': ['-ffp-contract=off'], 'gpa_unwrap_rowh
                'gpa_ucell.hip': ['-ffp-contract=off']}
 
 
+def flags_for(tu):
+    """The hipcc flags of one translation unit ('gpa_sweep' or 'gpa_sweep.hip'): the recipe of the shipped object, which the
+    variant builds and the static-analysis scripts under tools/ share."""
+    name = os.path.basename(tu)
+    return FLAGS + EXTRA_FLAGS.get(name if name.endswith('.hip') else name + '.hip', [])
+
+
 def _hipcc():
     for cand in (os.environ.get('HIPCC'), shutil.which('hipcc'), '/opt/rocm/bin/hipcc'):
         if cand and os.path.exists(cand):
@@ -73,7 +80,7 @@ def build(force=False, jobs=None, verbose=True):
 
     def compile_one(item):
         src, obj = item
-        cmd = [hipcc] + FLAGS + EXTRA_FLAGS.get(os.path.basename(src), []) + ['-c', src, '-o', obj]
+        cmd = [hipcc] + flags_for(src) + ['-c', src, '-o', obj]
         if verbose:
             print(' '.join(cmd), flush=True)
         r = subprocess.run(cmd, capture_output=True, text=True)

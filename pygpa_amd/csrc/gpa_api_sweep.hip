@@ -72,8 +72,8 @@ int passB_select(gpa_plan* p, const XPlanes& xp, int P, int K, void* lockin, int
     if (p->sh_use) {
       p->lk_raw = raw && !opt_set(OPT_NO_RAW) && p->sh_one_kref;
       HIP_TRY(launch_passB_shared(p->dtype, p->ax1s, p->n0, xp.T, p->ax1s.L == p->ax1.L ? p->tw1 : p->tw1s, p->tb,
-                                  p->sh, p->sh_E, p->sh_Epad, P, K, lockin, kidx, p->stream, xp.nimg, xp.stride, p->sh_elems,
-                                  p->sh_nbl, p->lk_raw));
+                                  p->sh, p->sh_E, p->sh_Epad, P, K, lockin, kidx, p->stream, xp.nimg, xp.stride, p->sh_nbl,
+                                  p->lk_raw));
     } else
       HIP_TRY(launch_passB(p->dtype, p->ax1, p->n0, xp.T, p->Hy, p->tw1, p->tb, P, K, true, lockin, kidx, p->stream, xp.nimg,
                            xp.stride));
@@ -100,7 +100,7 @@ int passB_phases(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, void* p
     if (p->sh_use && p->sh_one_kref) {
       const hipError_t e = launch_passB_shared_phases(p->dtype, p->ax1s, p->n0, p->Tbuf, p->ax1s.L == p->ax1.L ? p->tw1 : p->tw1s,
                                                       p->tb, p->sh, p->sh_E, p->sh_Epad, P, K, lockin, kidx, psi, p->stream, 0,
-                                                      p->sh_elems, p->sh_nbl);
+                                                      p->sh_nbl);
       if (e == hipSuccess) {
         *shared = true;
         return GPA_OK;

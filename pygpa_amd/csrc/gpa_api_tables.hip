@@ -189,7 +189,6 @@ int ensure_filters(gpa_plan* p, double sigma) {
           p->sh_etab = mmax;
           p->sh_E = E;
           p->sh_Epad = Epad;
-          p->sh_elems = passB_shared_elems(p->dtype, sa);
           p->sh_sigma = sigma;
           p->sh_ok = true;
         }
@@ -295,7 +294,7 @@ int shared_prepare(gpa_plan* p, int P, int K) {
   // outside |f + wy| < fc; over the candidates of a peak the live band is (-wy_max - fc, -wy_min + fc).  Rotating the
   // row by exp(-2 pi i s y / 16) and the candidates to wy + s / 16 moves that band down by s blocks of L / 16 bins:
   // s = the block the band starts in, so that it occupies blocks 0 .. need-1 -- the spectral registers the kernel keeps.
-  const int EEs = p->sh_elems;
+  const int EEs = 16;   // blocks of the spectral register layout = elements per thread of the kernel's row transform
   const double fc = sqrt(log(p->dtype == 0 ? 1e9 : 1e17) / (2.0 * M_PI * M_PI * p->sh_sigma * p->sh_sigma));
   std::vector<int> shifts((size_t)P, 0);
   std::vector<double> wys((size_t)B);
@@ -362,7 +361,7 @@ int shared_prepare(gpa_plan* p, int P, int K) {
   if (!p->sh.order) TRY(dmalloc(p, (void**)&p->sh.order, (size_t)p->max_batch * sizeof(int)));
   HIP_TRY(hipMemcpyAsync(p->sh.order, order.data(), (size_t)B * sizeof(int), hipMemcpyHostToDevice, p->stream));
   HIP_TRY(launch_shared_tables(p->dtype, p->ax1s, p->d_wys, p->d_kr, p->d_shifts, p->d_taps, p->sh_etab, p->sh_E, p->sh_Epad, B, K,
-                               p->sh_nbl, p->sh, p->stream, p->sh_elems));
+                               p->sh_nbl, p->sh, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));   // `desc`, `order` are locals
   p->sh_built_epoch = p->sh_epoch;
   p->sh_built_K = K;

@@ -6,6 +6,13 @@
 #include "gpa_fft.h"
 #include "gpa_mrfft.h"
 
+// Waves per SIMD the launch bounds of the f64 transform kernels ask for -- pass B of the sweep (gpa_passb.h) and the packed-pair
+// row kernels of the unwrap (gpa_unwrap_rows.hip, gpa_unwrap_pqdct.hip): 2, i.e. a cap of 256 VGPRs.  The one definition:
+// a -D override reaches every kernel that reads it.
+#ifndef GPA_F64_WAVES
+#define GPA_F64_WAVES 2
+#endif
+
 namespace gpa {
 
 // ---- per-kernel timing (bench.py's per-kernel rooflines) ----------------------------------------
@@ -84,7 +91,7 @@ inline int device_cus() {
 // A switch is "set" when it has a value at all (GPA_NO_LAT=0 is set, as it always was); num = atof(value).
 enum OptKey {
   OPT_PBS_FULLBAND, OPT_SERIAL_UNWRAP, OPT_NO_WORKER, OPT_NO_KSPLIT, OPT_NO_COMPACT, OPT_NO_SHARED,
-  OPT_NO_PAIR, OPT_PBS_E8, OPT_TRI_SMALL, OPT_TRI_Q, OPT_NO_MR, OPT_MR_FORCE_BLUESTEIN, OPT_NO_ROWPQ,
+  OPT_NO_PAIR, OPT_TRI_SMALL, OPT_TRI_Q, OPT_NO_MR, OPT_MR_FORCE_BLUESTEIN, OPT_NO_ROWPQ,
   OPT_COLSOLVE, OPT_NO_LAT, OPT_F32_EPS_FLOOR, OPT_COLSTREAM_CHUNK, OPT_NO_ROWHALF, OPT_PAIR_MAXSIDE, OPT_ROWHALF_MINLG, OPT_NO_PQDCT,
   OPT_NO_REORDER, OPT_NO_RAW, OPT_NO_TILEFUSE, OPT_NO_ROWPERS, OPT_NO_LFTILE, OPT_LF_ALL_ROUNDS, OPT_DFT_ENGINE, OPT_GAUSS_FFT_MINR, OPT_NO_GAUSS2D, OPT_NO_DFT_HALF, OPT_F32_STALL, OPT_PBS_LDS_PAD, OPT_NO_SHARED_PHASES, OPT_PA_STAG, OPT_PA_STAG_TICKS, OPT_PA_ROT, OPT_COUNT
 };

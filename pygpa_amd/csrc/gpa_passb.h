@@ -50,9 +50,7 @@ template <class T, int LG, bool PADDED, int MODE>
 #ifndef GPA_PASSB_PADDED_WAVES
 #define GPA_PASSB_PADDED_WAVES 3   // f32, padded axis: the selects of the extension slots push hipcc to 200 VGPRs (2 waves); capped at 168
 #endif
-#ifndef GPA_F64_WAVES
-#define GPA_F64_WAVES 2   // f64: cap at 256 VGPRs (2 waves/SIMD) instead of 299 at 1 wave: pass B 7.5 -> 5.9 ms
-#endif
+// (f64, GPA_F64_WAVES of gpa_internal.h: capped at 256 VGPRs instead of 299 at 1 wave: pass B 7.5 -> 5.9 ms)
 __global__ __launch_bounds__((PassBGeom<T, LG>::THREADS), (sizeof(T) == 8 ? GPA_F64_WAVES : (PADDED ? GPA_PASSB_PADDED_WAVES : 1))) void passB_kernel(
     const cpx<T>* __restrict__ Tin, int n0, int n1,
     const typename HType<PADDED, T>::type* __restrict__ H, const cpx<T>* __restrict__ twtab,

@@ -29,25 +29,22 @@ struct PassBSharedTables {
 
 // can the shared pass B run this axis (3-pass transforms, taps that vanish beyond E <= L / 16 samples, LDS)?
 bool passB_shared_supports(int dtype, const Axis& a1, int E);
-int passB_shared_elems(int dtype, const Axis& a1);
 
 // wys: device [B] doubles wy_b + shift(peak) / 16; kr: device [B][2] peaks of the candidates; shifts: device [P] ints, the
 // band rotation of every peak in blocks of L / 16 bins; taps: device doubles g(0 .. Etab) of the length-n circular filter;
 // nbl: live spectral registers (passB_shared_nbl)
 hipError_t launch_shared_tables(int dtype, const Axis& a1, const double* wys, const double* kr, const int* shifts,
                                 const double* taps, int Etab, int E, int Epad, int B, int K, int nbl, const PassBSharedTables& st,
-                                hipStream_t s, int elems = 16);
+                                hipStream_t s);
 int passB_shared_nbl(int dtype, int need);
 
-// elems: elements per thread of the row transform (16; 8 exists for 4096-point rows), the same value in
-// launch_shared_tables (the candidate tables are laid out for it).
 // a1: the shared kernel's own geometry of the y axis (periodic, or zero-padded to L >= n + E); tw1: twiddles of a1.L
 hipError_t launch_passB_shared(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* tw1, const SweepTables& tb,
                                const PassBSharedTables& st, int E, int Epad, int P, int K, void* out, int32_t* kidx,
-                               hipStream_t s, int nimg = 1, int Bx = 0, int elems = 16, int nbl = 16, bool raw = false);
+                               hipStream_t s, int nimg = 1, int Bx = 0, int nbl = 16, bool raw = false);
 hipError_t launch_passB_shared_phases(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* tw1, const SweepTables& tb,
                                       const PassBSharedTables& st, int E, int Epad, int P, int K, void* out, int32_t* kidx,
-                                      void* psi_out, hipStream_t s, int Bx, int elems, int nbl);
+                                      void* psi_out, hipStream_t s, int Bx, int nbl);
 // raw: the winners are left WITHOUT the candidate-independent compensation exp(2 pi i (ky + s_p / 16) y) (no second visit
 // of the rows: 0.8 GB less traffic at 4096^2 x 3); the consumer adds its phase step along y (launch_reconstruct_setup)
 

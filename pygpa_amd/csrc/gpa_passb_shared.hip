@@ -54,22 +54,6 @@ template <class T> __device__ __forceinline__ int mfma_row(int kq, int r) {
 
 template <class T> struct upair { T u, v; };
 
-#ifndef GPA_PBS_NOFIX
-#define GPA_PBS_NOFIX 0     // diagnosis only: skip the end fix (wrong results at the row ends)
-#endif
-#ifndef GPA_PBS_EXECSTORE
-#define GPA_PBS_EXECSTORE 0  // experiment: winners stored under the EXEC mask instead of through dropped offsets
-#endif
-#ifndef GPA_PBS_NOSTORE
-#define GPA_PBS_NOSTORE 0   // diagnosis only: skip the winner stores
-#endif
-#ifndef GPA_PBS_WAVESKIP
-#define GPA_PBS_WAVESKIP 1   // a register with no winning lane in the wavefront issues no store
-#endif
-#ifndef GPA_PBS_NTLOAD
-#define GPA_PBS_NTLOAD 1    // the x-plane row (read once) as a non-temporal load, so that it does not evict the winners' rows from L2 (-2.5 %, L2 hit rate 0.69 -> 0.80)
-#endif
-
 // the shifted Gaussian of one candidate: sixteen reals per thread in the spectral register layout
 template <class T, int TPF, int EE>
 __device__ __forceinline__ void load_gb(T (&h)[EE], const T* gbrow, int tid) {
@@ -122,9 +106,12 @@ __device__ __forceinline__ void store_cpx(cpx<double> v, __amdgpu_buffer_rsrc_t 
   __builtin_amdgcn_raw_buffer_store_b128(d, r, voff, soff, 0);
 }
 
-// EE = elements per thread of the row transform: 16 (256 threads per 4096-point row, three passes) or 8 (512 threads,
-// four passes: half the registers per thread -- the shared spectrum, the working copy and |best|^2 are per-element
-// arrays -- for one more exchange per transform)
+// EE = elements per thread of the row transform: 16 in every instantiation (256 threads per 4096-point row, three passes).
+// (Eight per thread -- 512 threads, four passes, half the registers for one more exchange per transform -- measured slower
+//  and a tie on re-measurement: profiles/r03_passB_variants.txt, profiles/r05_sweep_variants.txt; git history has it.)
+#ifndef GPA_PBS_MINTHREADS
+#define GPA_PBS_MINTHREADS 128   // also read by passB_shared_supports
+#endif
 template <class T, int LG, int EE = 16>
 struct PassBSGeom {
   using F = WgFFT<T, LG, EE>;
@@ -133,9 +120,6 @@ struct PassBSGeom {
   static_assert(TPF >= 64, "a row needs whole wavefronts");
   // (2048-point rows, 128 threads each: ONE row per workgroup -- two rows per workgroup cost a third of the occupancy
   //  to LDS: 514 -> 428 us at 2048^2, 3 x 8)
-#ifndef GPA_PBS_MINTHREADS
-#define GPA_PBS_MINTHREADS 128
-#endif
   static constexpr int NF = TPF >= GPA_PBS_MINTHREADS ? 1 : GPA_PBS_MINTHREADS / TPF;   // rows per workgroup
   static constexpr int THREADS = NF * TPF;
   static constexpr int NW = TPF / 64;                      // wavefronts per row
@@ -145,10 +129,7 @@ struct PassBSGeom {
   // in LDS once per chunk of NC candidates, so that neither the matrix pass nor the fix-up waits on global loads
   // (which queue behind the winner stores in vmcnt).  f64 has no LDS left for that at 4096 points.
   static constexpr bool STAGE = sizeof(T) == 4;
-#ifndef GPA_PBS_TWL
-#define GPA_PBS_TWL 1
-#endif
-  static constexpr bool TWL = GPA_PBS_TWL && F::P == 3;    // pass-1 twiddles from an LDS table (three-pass transforms)
+  static constexpr bool TWL = F::P == 3;                   // pass-1 twiddles from an LDS table (three-pass transforms)
   static constexpr int T1 = TWL ? F::P1_SETS * 6 : 0;      // that table (complex), one per workgroup
   // end strips: f32 keeps the four (end, re/im) forms the matrix pass multiplies directly, f64 (no LDS to spare at
   // 4096 points) the two complex strips and forms them per lane with selects
@@ -175,13 +156,6 @@ struct PassBSGeom {
 #ifndef GPA_PBS_F64_WAVES
 #define GPA_PBS_F64_WAVES 2
 #endif
-
-#ifndef GPA_PBS_E8_WAVES
-#define GPA_PBS_E8_WAVES 4    // eight elements per thread, f32: 128 VGPRs
-#endif
-#ifndef GPA_PBS_E8_F64_WAVES
-#define GPA_PBS_E8_F64_WAVES 2
-#endif
 // NBL = live spectral registers.  The Gaussian keeps a band of bins; in the spectral register layout register i of
 // every thread holds bin kappa(thread) + (L / EE) i, i.e. block i of L / EE consecutive bins.  The host rotates each
 // peak's band to block 0 (an input phasor exp(-2 pi i s y / EE) of period EE and candidate frequencies wy + s / EE: the
@@ -197,8 +171,7 @@ struct PassBSGeom {
 // subtracts that phasor's phase step per column and needs no 2 pi (w - k) (launch_phasegrad, compensated form).
 template <class T, int LG, bool PADDED, int EE, int NBL, bool PSI = false>
 __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
-                             (EE == 8 ? (sizeof(T) == 8 ? GPA_PBS_E8_F64_WAVES : GPA_PBS_E8_WAVES)
-                                      : (sizeof(T) == 8 ? GPA_PBS_F64_WAVES : (LG >= 13 ? GPA_PBS_L13_WAVES : (PADDED ? GPA_PBS_PAD_WAVES : GPA_PBS_F32_WAVES))))) void passB_shared_kernel(
+                             (sizeof(T) == 8 ? GPA_PBS_F64_WAVES : (LG >= 13 ? GPA_PBS_L13_WAVES : (PADDED ? GPA_PBS_PAD_WAVES : GPA_PBS_F32_WAVES)))) void passB_shared_kernel(
     const cpx<T>* __restrict__ Tin, int n0, int n1, const T* __restrict__ Gb, const cpx<T>* __restrict__ twtab,
     const int* __restrict__ planeof, const int* __restrict__ order, const int* __restrict__ desc, const cpx<T>* __restrict__ pre_g,
     const cpx<T>* __restrict__ psi, const T* __restrict__ gtab, const cpx<T>* __restrict__ dx,
@@ -231,10 +204,7 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
   // (pass-1 twiddles: from the LDS table where registers are short -- f64, zero-padded rows -- and in registers for
   //  periodic f32 rows, which have had 20 registers to spare at 3 waves per SIMD since the winner stores became rare:
   //  1.227 -> 1.203 ms; the table's LDS stays allocated either way, the geometry does not know PADDED)
-#ifndef GPA_PBS_TWREG_F32
-#define GPA_PBS_TWREG_F32 1
-#endif
-  constexpr bool TWLK = G::TWL && !(GPA_PBS_TWREG_F32 && sizeof(T) == 4 && !PADDED);
+  constexpr bool TWLK = G::TWL && !(sizeof(T) == 4 && !PADDED);
   typename std::conditional<TWLK, typename F::TwiddlesP1Lds, typename F::Twiddles>::type tw;
   if constexpr (TWLK) {
     F::fill_pass1_table(t1, twtab, threadIdx.x, G::THREADS);
@@ -265,13 +235,7 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
   // (f64: no prefetch since the stores became rare -- visiting order + wave-level skip -- so that loads issued behind them
   //  no longer wait for sixteen acknowledgements; the 16 registers it frees take the kernel from 68 to 12 bytes of
   //  scratch: pass B 3.06 -> 2.89 ms.  f32 measured the same either way and keeps it.)
-#ifndef GPA_PBS_PREFETCH_F64
-#define GPA_PBS_PREFETCH_F64 0
-#endif
-#ifndef GPA_PBS_PREFETCH_F32
-#define GPA_PBS_PREFETCH_F32 1
-#endif
-  constexpr bool PREFETCH = NBL < EE && (sizeof(T) == 8 ? GPA_PBS_PREFETCH_F64 : GPA_PBS_PREFETCH_F32);
+  constexpr bool PREFETCH = NBL < EE && sizeof(T) == 4;
   for (int k = 0; k < K; ++k) {
     const int b = pt * K + k;      // position in visiting order: the candidate tables of this file
     const int ob = order[b];       // its position in the staged list: x-plane, compensation along x, reported index
@@ -284,15 +248,17 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
       cpx<T> tail = {T(0), T(0)};
       if (tid < E) tail = src[n1 - 1 - tid];
       cpx<T> XX[EE];
+      // (the row is read once: non-temporal loads, so that it does not evict the winners' rows from L2 -- -2.5 %, L2 hit
+      //  rate 0.69 -> 0.80)
       if constexpr (PADDED) {
         // (zero-padded rows: the slots beyond the row read as zero through the range check of a buffer descriptor)
         const __amdgpu_buffer_rsrc_t srow = __builtin_amdgcn_make_buffer_rsrc((void*)src, 0, n1 * (int)sizeof(cpx<T>), 0x00020000);
 #pragma unroll
         for (int i = 0; i < EE; ++i)
-          XX[i] = cmul(load_cpx<T>(srow, (tid + TPF * i) * (int)sizeof(cpx<T>), 0, GPA_PBS_NTLOAD ? 2 : 0), cs);
+          XX[i] = cmul(load_cpx<T>(srow, (tid + TPF * i) * (int)sizeof(cpx<T>), 0, 2), cs);
       } else {
 #pragma unroll
-        for (int i = 0; i < EE; ++i) XX[i] = cmul(GPA_PBS_NTLOAD ? load_once(src + tid + TPF * i) : src[tid + TPF * i], cs);
+        for (int i = 0; i < EE; ++i) XX[i] = cmul(load_once(src + tid + TPF * i), cs);
       }
       if (tid < Epad) {
         // strips in the two forms the matrix pass reads (it forms ONE real of t * p or t * conj(p) per lane as
@@ -346,7 +312,7 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
     }
     F::template inv_phase<0>(y, lds, tid, tw);
     __syncthreads();
-    if ((d & 2) && !GPA_PBS_NOFIX) {
+    if (d & 2) {
       // end-fix contraction for the candidates b .. b + nc - 1: D[a][n] = sum_j g(a + 1 + j) B[j][n], column
       // n = (end, candidate, re/im).  Lane l supplies A[l & 15][l >> 4] and B[l >> 4][l & 15] of each k-step.
       const int nc = (d >> 4) & 7;
@@ -404,7 +370,6 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
       F::template inv_phase<3>(y, lds, tid, tw);
     }
     // ---- the outputs within E of either end get their wrapped pairs ------------------------------------------
-#if !GPA_PBS_NOFIX
     {
       const int c = (d >> 2) & 3;
       const cpx<T>* pl = psi_l + (par * NC + c) * ES;
@@ -445,7 +410,6 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
         }
       }
     }
-#endif
     // the next candidate's Gaussian (NBL values) is requested BEFORE this candidate's stores: vmcnt counts loads and
     // stores in order, so loads issued behind the stores would wait for the stores' acknowledgements as well
     if constexpr (PREFETCH) {
@@ -464,29 +428,22 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
     }
     // ---- strict '>' in visiting order; the winner goes to memory at once ------------------------------------
     // (a register none of whose 64 lanes wins issues no store at all: with the likeliest winners visited first that is
-    //  most registers of most candidates -- GPA_PBS_WAVESKIP=0 restores the sixteen dropped-offset stores per candidate)
+    //  most registers of most candidates)
 #pragma unroll
     for (int i = 0; i < EE; ++i) {
       const int yy = tid + TPF * i;
       const T a = y[i].x * y[i].x + y[i].y * y[i].y;
       const bool win = a > ab[i];
       ab[i] = win ? a : ab[i];
-#if GPA_PBS_WAVESKIP
       if (__builtin_amdgcn_ballot_w64(win) == 0) continue;
-#endif
       // (byte offset; OOB = 0x80000000 stays out of range after the arithmetic shift below, never multiply it)
       // (zero-padded rows: the whole column offset goes into the range-checked voffset, so that the slots beyond
       //  the row are dropped by the descriptor's num_records; soffset is not range checked)
       const int woff = (win && valid) ? (PADDED ? yy : tid) * (int)sizeof(cpx<T>) : OOB;
       constexpr int SOFF = PADDED ? 0 : 1;
-#if GPA_PBS_EXECSTORE
-      if (woff != OOB) store_cpx(y[i], orow, woff, SOFF * i * TPF * (int)sizeof(cpx<T>));
-      if (kidx && woff != OOB) __builtin_amdgcn_raw_buffer_store_b32(kout, krow, woff >> (sizeof(cpx<T>) == 8 ? 1 : 2), SOFF * i * TPF * 4, 0);
-#elif !GPA_PBS_NOSTORE
       store_cpx(y[i], orow, woff, SOFF * i * TPF * (int)sizeof(cpx<T>));
       constexpr int SH = sizeof(cpx<T>) == 8 ? 1 : 2;   // complex byte offset -> int32 byte offset
       if (kidx) __builtin_amdgcn_raw_buffer_store_b32(kout, krow, woff >> SH, SOFF * i * TPF * 4, 0);
-#endif
     }
   }
   if (!valid) return;
@@ -601,17 +558,12 @@ static hipError_t run_shared_tables(const Axis& a1, const double* wys, const dou
 
 hipError_t launch_shared_tables(int dtype, const Axis& a1, const double* wys, const double* kr, const int* shifts,
                                 const double* taps, int Etab, int E, int Epad, int B, int K, int nbl, const PassBSharedTables& st,
-                                hipStream_t s, int elems) {
-#ifdef GPA_PBS_BUILD_E8      // the eight-element instantiations: measured slower (profiles/r03_passB_variants.txt), not built by default
-#define CASE_T8(LG) CASE_T(LG, 8)
-#else
-#define CASE_T8(LG)
-#endif
-#define CASE_T(LG, EE)                                                                                                  \
-  if (a1.lg == LG && elems == EE)                                                                                       \
-    return dtype == 0 ? run_shared_tables<float, LG, EE>(a1, wys, kr, shifts, taps, Etab, E, Epad, B, K, nbl, st, s)    \
-                      : run_shared_tables<double, LG, EE>(a1, wys, kr, shifts, taps, Etab, E, Epad, B, K, nbl, st, s);
-  CASE_T(11, 16) CASE_T(12, 16) CASE_T(13, 16) CASE_T8(12)
+                                hipStream_t s) {
+#define CASE_T(LG)                                                                                                      \
+  if (a1.lg == LG)                                                                                                      \
+    return dtype == 0 ? run_shared_tables<float, LG, 16>(a1, wys, kr, shifts, taps, Etab, E, Epad, B, K, nbl, st, s)    \
+                      : run_shared_tables<double, LG, 16>(a1, wys, kr, shifts, taps, Etab, E, Epad, B, K, nbl, st, s);
+  CASE_T(11) CASE_T(12) CASE_T(13)
 #undef CASE_T
   return hipErrorInvalidValue;
 }
@@ -644,18 +596,6 @@ static hipError_t run_passB_shared(const Axis& a1, int n0, const void* Tbuf, con
   return hipGetLastError();
 }
 
-// elements per thread the kernel runs this axis with
-int passB_shared_elems(int dtype, const Axis& a1) {
-  (void)dtype;
-#ifdef GPA_PBS_BUILD_E8
-  const bool e8 = opt_set(OPT_PBS_E8);   // experiment switch
-  return (a1.lg == 12 && e8) ? 8 : 16;
-#else
-  (void)a1;
-  return 16;
-#endif
-}
-
 bool passB_shared_supports(int dtype, const Axis& a1, int E) {
   // 1024-point rows (one wavefront per row: the whole matrix pass and both end fixes on it) measured slower than
   // the per-candidate kernel (1024^2, 3 x 16: 189 against 131 us): from 2048 points on
@@ -685,17 +625,17 @@ int passB_shared_nbl(int dtype, int need) {
 // psi_out [P][K (list positions)][n0][n1] reals.  Instantiated for the row classes the pipeline uses (2048 / 4096 / f32 8192).
 hipError_t launch_passB_shared_phases(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* tw1, const SweepTables& tb,
                                       const PassBSharedTables& st, int E, int Epad, int P, int K, void* out, int32_t* kidx,
-                                      void* psi_out, hipStream_t s, int Bx, int elems, int nbl) {
+                                      void* psi_out, hipStream_t s, int Bx, int nbl) {
   if (!psi_out || !kidx) return hipErrorInvalidValue;
-#define CALL_P(T, LG, EE, NBL) \
-  (a1.padded ? run_passB_shared<T, LG, true, EE, NBL, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, 1, Bx, false, psi_out) \
-             : run_passB_shared<T, LG, false, EE, NBL, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, 1, Bx, false, psi_out))
-#define CASE_P(LG, EE, NBL) \
-  if (a1.lg == LG && elems == EE && nbl == NBL) return dtype == 0 ? CALL_P(float, LG, EE, NBL) : CALL_P(double, LG, EE, NBL);
-#define CASE_PF32(LG, EE, NBL) \
-  if (a1.lg == LG && elems == EE && nbl == NBL && dtype == 0) return CALL_P(float, LG, EE, NBL);
-  CASE_PF32(11, 16, 6) CASE_PF32(12, 16, 6) CASE_PF32(13, 16, 6) CASE_PF32(13, 16, 8) CASE_PF32(13, 16, 16)
-  CASE_P(11, 16, 8) CASE_P(12, 16, 8) CASE_P(11, 16, 16) CASE_P(12, 16, 16)
+#define CALL_P(T, LG, NBL) \
+  (a1.padded ? run_passB_shared<T, LG, true, 16, NBL, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, 1, Bx, false, psi_out) \
+             : run_passB_shared<T, LG, false, 16, NBL, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, 1, Bx, false, psi_out))
+#define CASE_P(LG, NBL) \
+  if (a1.lg == LG && nbl == NBL) return dtype == 0 ? CALL_P(float, LG, NBL) : CALL_P(double, LG, NBL);
+#define CASE_PF32(LG, NBL) \
+  if (a1.lg == LG && nbl == NBL && dtype == 0) return CALL_P(float, LG, NBL);
+  CASE_PF32(11, 6) CASE_PF32(12, 6) CASE_PF32(13, 6) CASE_PF32(13, 8) CASE_PF32(13, 16)
+  CASE_P(11, 8) CASE_P(12, 8) CASE_P(11, 16) CASE_P(12, 16)
 #undef CASE_PF32
 #undef CASE_P
 #undef CALL_P
@@ -704,19 +644,16 @@ hipError_t launch_passB_shared_phases(int dtype, const Axis& a1, int n0, const v
 
 hipError_t launch_passB_shared(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* tw1, const SweepTables& tb,
                                const PassBSharedTables& st, int E, int Epad, int P, int K, void* out, int32_t* kidx,
-                               hipStream_t s, int nimg, int Bx, int elems, int nbl, bool raw) {
-#define CALL_S(T, LG, EE, NBL) \
-  (a1.padded ? run_passB_shared<T, LG, true, EE, NBL>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, raw) \
-             : run_passB_shared<T, LG, false, EE, NBL>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, raw))
-#define CASE_S(LG, EE, NBL) \
-  if (a1.lg == LG && elems == EE && nbl == NBL) return dtype == 0 ? CALL_S(float, LG, EE, NBL) : CALL_S(double, LG, EE, NBL);
-#define CASE_F32(LG, EE, NBL) \
-  if (a1.lg == LG && elems == EE && nbl == NBL && dtype == 0) return CALL_S(float, LG, EE, NBL);
-  CASE_F32(11, 16, 6) CASE_F32(12, 16, 6) CASE_F32(13, 16, 6) CASE_F32(13, 16, 8) CASE_F32(13, 16, 16)
-  CASE_S(11, 16, 8) CASE_S(12, 16, 8) CASE_S(11, 16, 16) CASE_S(12, 16, 16)
-#ifdef GPA_PBS_BUILD_E8
-  CASE_S(12, 8, 8)
-#endif
+                               hipStream_t s, int nimg, int Bx, int nbl, bool raw) {
+#define CALL_S(T, LG, NBL) \
+  (a1.padded ? run_passB_shared<T, LG, true, 16, NBL>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, raw) \
+             : run_passB_shared<T, LG, false, 16, NBL>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, raw))
+#define CASE_S(LG, NBL) \
+  if (a1.lg == LG && nbl == NBL) return dtype == 0 ? CALL_S(float, LG, NBL) : CALL_S(double, LG, NBL);
+#define CASE_F32(LG, NBL) \
+  if (a1.lg == LG && nbl == NBL && dtype == 0) return CALL_S(float, LG, NBL);
+  CASE_F32(11, 6) CASE_F32(12, 6) CASE_F32(13, 6) CASE_F32(13, 8) CASE_F32(13, 16)
+  CASE_S(11, 8) CASE_S(12, 8) CASE_S(11, 16) CASE_S(12, 16)
 #undef CASE_F32
 #undef CASE_S
 #undef CALL_S

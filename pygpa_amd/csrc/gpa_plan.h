@@ -117,7 +117,6 @@ struct gpa_plan {
   PassBSharedTables sh{};
   double* d_taps = nullptr;       // g(0 .. sh_etab) of the y axis' circular filter, doubles
   int sh_etab = 0, sh_E = 0, sh_Epad = 0;
-  int sh_elems = 16;              // elements per thread of its row transform (8 for 4096-point rows, see passB_shared_elems)
   int sh_nbl = 16;                // live spectral registers of the staged candidates (band rotation, passB_shared_nbl)
   double sh_sigma = 0.0;          // the sigma the taps belong to (band cut-off)
   double* d_wys = nullptr;        // [max_batch] candidate frequencies wy + rotation

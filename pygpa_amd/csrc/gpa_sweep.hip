@@ -308,15 +308,8 @@ __global__ __launch_bounds__((PassAGeom<T, LG>::THREADS)) void passA_kernel(
             *reinterpret_cast<Pair*>(&Tout[((size_t)b * n0 + slot) * n1 + y0]) = pr;
           }
         };
-        {
 #pragma unroll
-          for (int i = 0; i < 16; ++i) {
-#ifdef GPA_PA_NOSTORE
-            if (i > 0) continue;   // diagnosis only
-#endif
-            put(i);
-          }
-        }
+        for (int i = 0; i < 16; ++i) put(i);
       }
     }
     if (!paired) {

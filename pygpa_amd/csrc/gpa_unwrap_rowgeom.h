@@ -6,13 +6,11 @@
 namespace gpa {
 namespace {
 
-#ifndef GPA_ROW_TWLDS
-#define GPA_ROW_TWLDS 1   // 16-element three-pass row transforms: pass-1 base twiddles from a small LDS table (12 VGPRs less in f32)
-#endif
 template <class T, int LG, bool LAT = false>
 struct RowGeom {
   using F = WgFFT<T, LG, unwrap_elems(LG, sizeof(T))>;
-  static constexpr bool TWLDS = GPA_ROW_TWLDS && F::E == 16 && F::P == 3;
+  // 16-element three-pass row transforms: pass-1 base twiddles from a small LDS table (12 VGPRs less in f32)
+  static constexpr bool TWLDS = F::E == 16 && F::P == 3;
   using TW = typename std::conditional<TWLDS, typename F::TwiddlesP1Lds, typename F::Twiddles>::type;
   static constexpr int T1N = TWLDS ? F::P1_SETS * 6 : 1;
   using D = WgDCT<T, LG, unwrap_elems(LG, sizeof(T))>;
@@ -32,9 +30,7 @@ struct RowGeom {
   static constexpr size_t LDS_BYTES = (size_t)NF * RS * sizeof(cpx<T>);
   static constexpr bool FITS = LDS_BYTES <= 160 * 1024;
 };
-#ifndef GPA_F64_WAVES
-#define GPA_F64_WAVES 2   // f64 row kernels: 2 waves/SIMD (256 VGPRs) beat 1 wave with AGPR spill-over
-#endif
+// (f64 row kernels run at GPA_F64_WAVES of gpa_internal.h: 2 waves/SIMD, 256 VGPRs, beat 1 wave with AGPR spill-over)
 
 }  // namespace
 }  // namespace gpa

@@ -81,10 +81,7 @@ __global__ __launch_bounds__((RowHalfGeom<T, LG>::THREADS), (sizeof(T) == 4 && L
   // the kept spectrum is requested before the transform so that its latency hides behind it -- except for f32 rows of
   // 16384 points, whose 128-register budget (two workgroups per CU) it would overrun: there it is requested after
   // the transform, and the other workgroup of the CU covers the wait
-#ifndef GPA_ROWHALF_LATE_R
-#define GPA_ROWHALF_LATE_R (sizeof(T) == 4 && LG == 14)
-#endif
-  constexpr bool LATE_R = GPA_ROWHALF_LATE_R;
+  constexpr bool LATE_R = sizeof(T) == 4 && LG == 14;
   // The post-processing owns its bins in BLOCKS OF FOUR: thread t, block v holds k = 4 (t + TPF v) + e, e = 0 .. 3, and their
   // partners N - k -- so the kept spectrum comes in and goes out as 16-byte accesses (the partners' vector starts at N - k0 - 3:
   // 4-byte aligned, which global memory takes) and the two tables as 32 bytes per block.  (Rounds 3-5 owned k = t + TPF i:

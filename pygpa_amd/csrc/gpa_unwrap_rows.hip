@@ -13,12 +13,6 @@ namespace {
 #ifndef GPA_DCTF_WAVES
 #define GPA_DCTF_WAVES 1
 #endif
-#ifndef GPA_EARLY16
-#define GPA_EARLY16 0   // experiment: the every-input-first kernel variants also for 16-element transforms
-#endif
-#ifndef GPA_F64_WAVES
-#define GPA_F64_WAVES 2   // f64 row kernels: 2 waves/SIMD (256 VGPRs) beat 1 wave with AGPR spill-over
-#endif
 // LAT: the latency-tuned variant (one image per call, axes up to 1024) -- same arithmetic, same results
 template <class T, int LG, bool LAT = false>
 __global__ __launch_bounds__((RowGeom<T, LG, LAT>::THREADS), (sizeof(T) == 8 ? GPA_F64_WAVES : GPA_DCTF_WAVES)) void rowdct_fused_kernel(
@@ -48,7 +42,7 @@ __global__ __launch_bounds__((RowGeom<T, LG, LAT>::THREADS), (sizeof(T) == 8 ? G
   // init (first iteration of a solve on prepared residuals): part_pq / npq are the producer's partial norms of r0
   // EARLY (short transforms): every input of an update -- flags, q, the kept spectrum, w_k, partial sums, rho -- is
   // requested before anything waits, so the kernel pays one memory round trip instead of five in a row
-  constexpr bool EARLY = LAT && (E == 8 || GPA_EARLY16);
+  constexpr bool EARLY = LAT && E == 8;
   const bool early = EARLY && it > 0;
   int stop = 0;
   if (init) { if (!solve_init(part_pq, npq, scal, flags, sh)) return; }
@@ -59,20 +53,9 @@ __global__ __launch_bounds__((RowGeom<T, LG, LAT>::THREADS), (sizeof(T) == 8 ? G
   const int pr = blockIdx.x * G::NF + f;
   const bool valid = 2 * pr + 1 < n0;
   const size_t oa = (size_t)(valid ? 2 * pr : 0) * N, ob = oa + N;
-  // (register twiddles by default: the LDS table of rowidct_p_kernel made this kernel's allocation worse, 156 -> 160 VGPRs)
-#ifndef GPA_DCTF_TWLDS
-#define GPA_DCTF_TWLDS 0
-#endif
-  constexpr bool TWL = GPA_DCTF_TWLDS && G::TWLDS;
-  typename std::conditional<TWL, typename F::TwiddlesP1Lds, typename F::Twiddles>::type tw;
-  __shared__ cpx<T> t1s[TWL ? G::T1N : 1];
-  if constexpr (TWL) {
-    F::fill_pass1_table(t1s, twtab, threadIdx.x, G::THREADS);
-    __syncthreads();
-    F::load_twiddles(tw, twtab, tid, t1s);
-  } else {
-    F::load_twiddles(tw, twtab, tid);
-  }
+  // (register twiddles: the LDS table of rowidct_p_kernel made this kernel's allocation worse, 156 -> 160 VGPRs)
+  typename F::Twiddles tw;
+  F::load_twiddles(tw, twtab, tid);
   cpx<T> x[E];
   cpx<T> rk[E];
   cpx<T> wkv[EARLY ? E : 1];
@@ -147,12 +130,8 @@ __global__ __launch_bounds__((RowGeom<T, LG, LAT>::THREADS), (sizeof(T) == 8 ? G
     }
     __syncthreads();   // in place: every sample of the two rows is in registers before any bin is written
   }
-#ifndef GPA_DCTF_LATE_RK
-#define GPA_DCTF_LATE_RK 0
-#endif
   // the kept spectrum is requested before the transform so that its latency hides behind it
-  // (GPA_DCTF_LATE_RK: after it instead -- 32 registers less across the transform, one more wave per SIMD)
-  if (it > 0 && !early && !GPA_DCTF_LATE_RK) {
+  if (it > 0 && !early) {
 #pragma unroll
     for (int i = 0; i < E; ++i) rk[i] = {r[oa + tid + TPF * i], r[ob + tid + TPF * i]};
   }
@@ -162,10 +141,6 @@ __global__ __launch_bounds__((RowGeom<T, LG, LAT>::THREADS), (sizeof(T) == 8 ? G
   __syncthreads();
   if constexpr (EARLY) { if (early) D::fwd_gather(x, lds, tid, wkv); else D::fwd_gather(x, lds, tid, wk); }
   else D::fwd_gather(x, lds, tid, wk);
-  if (it > 0 && GPA_DCTF_LATE_RK) {
-#pragma unroll
-    for (int i = 0; i < E; ++i) rk[i] = {r[oa + tid + TPF * i], r[ob + tid + TPF * i]};
-  }
   double sq = 0;
 #pragma unroll
   for (int i = 0; i < E; ++i) {
@@ -194,14 +169,9 @@ __global__ __launch_bounds__((RowGeom<T, LG, LAT>::THREADS), (sizeof(T) == 8 ? G
 // rho from the column kernel's Parseval partial sums.
 // f32, 4096-point rows: 4 waves per SIMD (<= 128 VGPRs; the unconstrained allocation takes 130 and runs at 3):
 // 49 -> 43 us.  Other lengths would spill under that cap (2048: 13 -> 16 us) and keep the default.
+// (8192 points: 28 B of scratch buy a second workgroup per CU, -12 %)
 template <class T, int LG, bool LAT = false>
-#ifndef GPA_IDCTP_COND
-#define GPA_IDCTP_COND (sizeof(T) == 4 && (LG == 12 || LG == 13))   // (8192 points: 28 B of scratch buy a second workgroup per CU, -12 %)
-#endif
-#ifndef GPA_F64_WAVES
-#define GPA_F64_WAVES 2   // f64 row kernels: 2 waves/SIMD (256 VGPRs) beat 1 wave with AGPR spill-over
-#endif
-__global__ __launch_bounds__((RowGeom<T, LG, LAT>::THREADS), ((GPA_IDCTP_COND && !LAT) ? 4 : (sizeof(T) == 8 ? GPA_F64_WAVES : 1))) void rowidct_p_kernel(
+__global__ __launch_bounds__((RowGeom<T, LG, LAT>::THREADS), ((sizeof(T) == 4 && (LG == 12 || LG == 13) && !LAT) ? 4 : (sizeof(T) == 8 ? GPA_F64_WAVES : 1))) void rowidct_p_kernel(
     const T* __restrict__ Z, const T* __restrict__ pin, T* __restrict__ pout, int n0,
     const cpx<T>* __restrict__ twtab, const cpx<T>* __restrict__ wk, const int* flags, const double* part_rho,
     int nrho, double* scal, int it, size_t pimg) {
@@ -224,7 +194,7 @@ __global__ __launch_bounds__((RowGeom<T, LG, LAT>::THREADS), ((GPA_IDCTP_COND &&
   constexpr int TPF = F::TPF, N = F::L, E = F::E;
   // (short transforms only: the long ones are bandwidth-bound, hide latency behind other workgroups and have no
   //  registers to spare for 2 E more values)
-  constexpr bool EARLY = LAT && (E == 8 || GPA_EARLY16);
+  constexpr bool EARLY = LAT && E == 8;
   if (!EARLY && stop) return;
   extern __shared__ __attribute__((aligned(16))) char smem[];
   __shared__ double sh[RowGeom<T, LG, LAT>::THREADS];

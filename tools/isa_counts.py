@@ -8,11 +8,12 @@ import sys
 import tempfile
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
+sys.path.insert(0, ROOT)
+from pygpa_amd.build import flags_for   # noqa: E402
 tu, subs = sys.argv[1], sys.argv[2:]
 out = os.path.join(tempfile.gettempdir(), tu + '.s')
-subprocess.run(['hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-fno-gpu-rdc', '-ffp-contract=fast', '-fno-slp-vectorize',
-                '-Wno-unused-result', '-Wno-unused-value', '--cuda-device-only', '-S', os.path.join(ROOT, 'pygpa_amd', 'csrc', tu + '.hip'),
-                '-o', out], capture_output=True)
+subprocess.run(['hipcc'] + flags_for(tu) + ['--cuda-device-only', '-S', os.path.join(ROOT, 'pygpa_amd', 'csrc', tu + '.hip'), '-o', out],
+               capture_output=True)
 txt = open(out).read()
 rows = []
 for m in re.finditer(r'\n(_Z\w+):[^\n]*\n(.*?)\n\.Lfunc_end', txt, re.S):

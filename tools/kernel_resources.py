@@ -7,11 +7,12 @@ import sys
 import os
 
 ROOT = os.path.join(os.path.dirname(os.path.abspath(__file__)), '..')
+sys.path.insert(0, ROOT)
+from pygpa_amd.build import flags_for   # noqa: E402
 tu = sys.argv[1]
 flt = sys.argv[2] if len(sys.argv) > 2 and not sys.argv[2].startswith('-') else ''
 extra = [a for a in sys.argv[2:] if a.startswith('-')]
-cmd = ['hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-fno-gpu-rdc', '-ffp-contract=fast', '-fno-slp-vectorize',
-       '-Wno-unused-result', '-Wno-unused-value', '-Rpass-analysis=kernel-resource-usage', '-c',
+cmd = ['hipcc'] + flags_for(tu) + ['-Rpass-analysis=kernel-resource-usage', '-c',
        os.path.join(ROOT, 'pygpa_amd', 'csrc', tu + '.hip'), '-o', '/dev/null'] + extra
 out = subprocess.run(cmd, capture_output=True, text=True).stderr
 cur = None

@@ -1,9 +1,11 @@
 #!/usr/bin/env python
-"""Print VGPR/AGPR/scratch/occupancy of selected kernels: python tools_resusage.py file.hip 'regex'"""
-import re, subprocess, sys
+"""Print VGPR/AGPR/scratch/occupancy of selected kernels: python tools/resusage.py pygpa_amd/csrc/file.hip 'regex'"""
+import os, re, subprocess, sys
+sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
+from pygpa_amd.build import flags_for   # noqa: E402
 src, pat = sys.argv[1], sys.argv[2]
-r = subprocess.run(['hipcc', '-O3', '-std=c++17', '-fPIC', '--offload-arch=gfx950', '-fno-gpu-rdc', '-ffp-contract=fast', '-fno-slp-vectorize',
-                    '-Rpass-analysis=kernel-resource-usage', '-I', 'pygpa_amd/csrc', '-c', src, '-o', '/tmp/_res.o'], capture_output=True, text=True)
+r = subprocess.run(['hipcc'] + flags_for(src) + ['-Rpass-analysis=kernel-resource-usage', '-I', 'pygpa_amd/csrc', '-c', src, '-o', '/tmp/_res.o'],
+                   capture_output=True, text=True)
 if r.returncode:
     print(r.stderr[-3000:]); sys.exit(1)
 blocks = re.split(r'remark: [^\n]*Function Name: ', r.stderr)[1:]
