@@ -332,6 +332,20 @@ int gpa_undistort_image_dev(gpa_plan* plan, const void* deformed_dev, const void
  * tests/test_geometric_phase_analysis.py:63, and undistort with the true one, :76).                                   */
 int gpa_undistort_image_scaled_dev(gpa_plan* plan, const void* deformed_dev, const void* u_dev, double scale,
                                    const int* rects, int nrect, void* uinv_dev, void* out_dev);
+/* undistort_image of a STACK of B frames (B x n0 x n1, contiguous; 1 <= B <= 65535, else GPA_ERR_ARG) in one call -- no
+ * counterpart in the reference, where a loop over undistort_image (geometric_phase_analysis.py:935-974) gives the same
+ * numbers.  u_per_frame == 0: u is 2 x n0 x n1, one field for every frame (a static detector distortion): it is
+ * prefiltered and inverted ONCE, the spline weights of a pixel are shared by the frames.  u_per_frame != 0: u is
+ * B x 2 x n0 x n1 (the output of gpa_extract_displacement_field_batch_dev as it stands: scale = -1), inverted in one set
+ * of launches per chunk.  uinv_dev (nullable) receives u_inv in the layout of u.  Frame b's result is bitwise what
+ * gpa_undistort_image_scaled_dev gives for it alone.  The frames pass through the plan's scratch in chunks whose spline
+ * planes fit 512 MiB (one frame at least; counted in gpa_plan_workspace_bytes); offsets into the stack are 64-bit.
+ * _dev: device pointers, enqueued on the plan's stream without a host synchronisation.  The host-pointer form undistorts
+ * with u itself (scale = 1), like gpa_undistort_image.                                                                */
+#define GPA_UNDISTORT_MAX_FRAMES 65535
+int gpa_undistort_image_batch_dev(gpa_plan* plan, const void* frames_dev, int B, const void* u_dev, int u_per_frame,
+                                  double scale, void* uinv_dev, void* out_dev);
+int gpa_undistort_image_batch(gpa_plan* plan, const void* frames, int B, const void* u, int u_per_frame, void* out);
 
 /* f-2 -- phase gradient -> Jacobian -> lattice properties.
  * gpa_phasegradient2J: J[n,m,i,j] = (per-pixel weighted least squares of grads[:,n,m,j] against

@@ -16,6 +16,7 @@ LIB_PATH = os.environ.get('GPA_HIP_LIB') or os.path.join(_HERE, 'libgpa_hip.so')
 
 GPA_F32, GPA_F64 = 0, 1
 UCELL_MAX_FRAMES = 65535     # frames of one gpa_unit_cell_average_batch_dev call
+UNDISTORT_MAX_FRAMES = 65535     # frames of one gpa_undistort_image_batch[_dev] call
 _DTYPES = {GPA_F32: (np.float32, np.complex64), GPA_F64: (np.float64, np.complex128)}
 
 # every symbol of include/gpa_hip.h: name -> (restype, argtypes)
@@ -45,6 +46,8 @@ SIGNATURES = {
     'gpa_invert_u_mode_dev': (_i, [_vp, _vp, _d, _i, _i, _i, _i, _vp, _i, _vp]),
     'gpa_undistort_image_dev': (_i, [_vp, _vp, _vp, _vp, _i, _vp, _vp]),
     'gpa_undistort_image_scaled_dev': (_i, [_vp, _vp, _vp, _d, _vp, _i, _vp, _vp]),
+    'gpa_undistort_image_batch_dev': (_i, [_vp, _vp, _i, _vp, _i, _d, _vp, _vp]),
+    'gpa_undistort_image_batch': (_i, [_vp, _vp, _i, _vp, _i, _vp]),
     'gpa_reconstruct_grad': (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     'gpa_reconstruct_grad_dev': (_i, [_vp, _vp, _vp, _i, _i, _vp, _vp, _vp]),
     'gpa_weighted_lstsq': (_i, [_vp, _vp, _vp, _vp, _i, _vp]),
@@ -222,6 +225,24 @@ def _peak_lists(kvecs, klists):
     return kvecs, P, klists, klists.shape[1]
 
 
+def stack_shapes(frames_shape, u_shape, plan_shape=None):
+    """The shapes undistort_image_stack takes: frames (B, N, M) with B >= 1, u (2, N, M) or (B, 2, N, M).  Returns
+    (B, per_frame); ValueError for any other combination (and for frames that do not match plan_shape, when given)."""
+    frames_shape, u_shape = tuple(frames_shape), tuple(u_shape)
+    if len(frames_shape) != 3 or frames_shape[0] < 1:
+        raise ValueError('frames must be a stack (B, N, M) with B >= 1, not %s' % (frames_shape,))
+    B, shape = frames_shape[0], frames_shape[1:]
+    if plan_shape is not None and shape != tuple(plan_shape):
+        raise ValueError('frames %s do not match the plan %s' % (shape, tuple(plan_shape)))
+    if u_shape == (2,) + shape:
+        return B, False
+    if len(u_shape) == 4 and u_shape[1:] == (2,) + shape:
+        if u_shape[0] != B:
+            raise ValueError('u holds %d fields for %d frames' % (u_shape[0], B))
+        return B, True
+    raise ValueError('u must be (2, N, M) or (B, 2, N, M) for frames (B, N, M) = %s, not %s' % (frames_shape, u_shape))
+
+
 class Plan:
     """One device + stream + workspace for images of a fixed shape (wraps gpa_plan)."""
 
@@ -378,6 +399,34 @@ class Plan:
         out = np.empty(self.shape, dtype=self.rdtype)
         check(self.lib.gpa_undistort_image(self.handle, _ptr(deformed), _ptr(u), _ptr(out)), 'gpa_undistort_image')
         return out
+
+    def undistort_image_stack(self, frames, u, chunk=None):
+        """undistort_image of every frame of `frames` (B, n0, n1) in one library call per `chunk` frames (default and
+        upper limit: the 65535 frames a call takes).  u: (2, n0, n1), one field for all frames -- inverted once per call --
+        or (B, 2, n0, n1), a field per frame.  Returns (B, n0, n1); frame b equals undistort_image(frames[b], u or u[b])
+        bitwise."""
+        frames, u = np.asarray(frames), np.asarray(u)
+        B, per_frame = stack_shapes(frames.shape, u.shape, self.shape)
+        chunk = UNDISTORT_MAX_FRAMES if chunk is None else max(1, min(int(chunk), UNDISTORT_MAX_FRAMES))
+        if not per_frame:
+            u = np.ascontiguousarray(u, dtype=self.rdtype)
+        out = np.empty((B,) + self.shape, dtype=self.rdtype)
+        for b0 in range(0, B, chunk):
+            nb = min(chunk, B - b0)
+            fr = np.ascontiguousarray(frames[b0:b0 + nb], dtype=self.rdtype)
+            uu = np.ascontiguousarray(u[b0:b0 + nb], dtype=self.rdtype) if per_frame else u
+            check(self.lib.gpa_undistort_image_batch(self.handle, _ptr(fr), nb, _ptr(uu), int(per_frame), _ptr(out[b0:b0 + nb])),
+                  'gpa_undistort_image_batch')
+        return out
+
+    def undistort_image_batch_dev(self, frames_ptr, nframes, u_ptr, out_ptr, per_frame=False, scale=1.0, uinv_ptr=None):
+        """undistort_image(frames[b], scale * u) of nframes plan-shaped frames (contiguous) on device pointers, enqueued on the
+        plan's stream (no host sync).  per_frame False: u is one field (2 x n0 x n1) for all frames; True: nframes fields
+        (nframes x 2 x n0 x n1), e.g. the output of extract_displacement_field_batch_dev with scale = -1.  uinv_ptr receives
+        u_inv in the layout of u.  nframes: 1 .. 65535"""
+        check(self.lib.gpa_undistort_image_batch_dev(self.handle, _ptr(int(frames_ptr)), int(nframes), _ptr(int(u_ptr)),
+                                                     int(bool(per_frame)), float(scale), _ptr(uinv_ptr), _ptr(int(out_ptr))),
+              'gpa_undistort_image_batch_dev')
 
     # ---- unit-cell averaging / expansion (unit_cell_averaging.py); geom: a UcellGeom -------------------------
     def unit_cell_average(self, image, geom, u=None, want_weights=False):

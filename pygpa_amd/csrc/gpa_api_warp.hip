@@ -71,6 +71,63 @@ int gpa_undistort_image_scaled_dev(gpa_plan* p, const void* deformed_dev, const 
   return GPA_OK;
 }
 
+// undistort_image of a stack (no counterpart in the reference: a loop over undistort_image, geometric_phase_analysis.py:935-974).
+// One field for all frames (u_per_frame == 0) is inverted once; the frames go through the plan's scratch in chunks.
+static int check_stack_args(gpa_plan* p, const void* frames, int B, const void* u, const void* out, const char* who) {
+  if (!p || !frames || !u || !out) return fail(GPA_ERR_ARG, std::string(who) + ": null argument");
+  if (B < 1 || B > GPA_UNDISTORT_MAX_FRAMES)
+    return fail(GPA_ERR_ARG, std::string(who) + ": B = " + std::to_string(B) + " frames, a call takes 1 .. " +
+                                 std::to_string(GPA_UNDISTORT_MAX_FRAMES) + " (split the stack)");
+  return GPA_OK;
+}
+
+int gpa_undistort_image_batch_dev(gpa_plan* p, const void* frames_dev, int B, const void* u_dev, int u_per_frame, double scale,
+                                  void* uinv_dev, void* out_dev) {
+  TRY(check_stack_args(p, frames_dev, B, u_dev, out_dev, "gpa_undistort_image_batch_dev"));
+  HIP_TRY(hipSetDevice(p->device));
+  ProfInstall prof(p);
+  p->warp.counted = &p->ws_bytes;
+  void* uinv = uinv_dev ? uinv_dev : (u_per_frame ? nullptr : p->d_dudx);   // (a shared u_inv: 2 planes of n0 x n1 fit)
+  HIP_TRY(warp_undistort_stack(p->dtype, frames_dev, B, u_dev, u_per_frame ? 1 : 0, scale, uinv, p->n0, p->n1, out_dev, p->stream, &p->warp));
+  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
+  return GPA_OK;
+}
+
+// the host-pointer form: the frames are staged through device buffers of one chunk (the scratch's chunk); a shared field is
+// uploaded and inverted before the first chunk
+int gpa_undistort_image_batch(gpa_plan* p, const void* frames, int B, const void* u, int u_per_frame, void* out) {
+  TRY(check_stack_args(p, frames, B, u, out, "gpa_undistort_image_batch"));
+  HIP_TRY(hipSetDevice(p->device));
+  const int per = u_per_frame ? 1 : 0;
+  const size_t pb = (size_t)p->n0 * p->n1 * p->rsz;
+  const int chunk = warp_stack_chunk(p->dtype, p->n0, p->n1, B, per);
+  char* d_stage = nullptr;      // chunk frames | chunk results | chunk fields (per frame)
+  HIP_TRY(hipMalloc(&d_stage, (size_t)chunk * pb * (per ? 4 : 2)));
+  char *d_fr = d_stage, *d_res = d_stage + (size_t)chunk * pb, *d_uf = d_res + (size_t)chunk * pb;
+  p->warp.counted = &p->ws_bytes;
+  hipError_t e = hipSuccess;
+  bool first = true;
+  for (int f0 = 0; f0 < B && e == hipSuccess; f0 += chunk, first = false) {
+    const int nb = std::min(chunk, B - f0);
+    e = hipMemcpyAsync(d_fr, (const char*)frames + (size_t)f0 * pb, (size_t)nb * pb, hipMemcpyHostToDevice, p->stream);
+    const void* d_u = nullptr;   // (shared field after the first chunk: p->d_dudx holds its inverse)
+    if (e == hipSuccess && per) {
+      e = hipMemcpyAsync(d_uf, (const char*)u + 2 * (size_t)f0 * pb, 2 * (size_t)nb * pb, hipMemcpyHostToDevice, p->stream);
+      d_u = d_uf;
+    } else if (e == hipSuccess && first) {
+      e = hipMemcpyAsync(p->d_u, u, 2 * pb, hipMemcpyHostToDevice, p->stream);
+      d_u = p->d_u;
+    }
+    if (e == hipSuccess)
+      e = warp_undistort_stack(p->dtype, d_fr, nb, d_u, per, 1.0, per ? nullptr : p->d_dudx, p->n0, p->n1, d_res, p->stream, &p->warp);
+    if (e == hipSuccess) e = hipMemcpyAsync((char*)out + (size_t)f0 * pb, d_res, (size_t)nb * pb, hipMemcpyDeviceToHost, p->stream);
+    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);   // (pageable memory: the copies are synchronous anyway)
+  }
+  (void)hipFree(d_stage);
+  if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_undistort_image_batch: ") + hipGetErrorString(e));
+  return GPA_OK;
+}
+
 static int invert_u_host(gpa_plan* p, const void* u, int iters, int edge, int overlap, int mode, void* out) {
   TRY(check_invert_args(p, u, out, iters, edge, mode));
   HIP_TRY(hipSetDevice(p->device));

@@ -93,7 +93,7 @@ enum OptKey {
   OPT_PBS_FULLBAND, OPT_SERIAL_UNWRAP, OPT_NO_WORKER, OPT_NO_KSPLIT, OPT_NO_COMPACT, OPT_NO_SHARED,
   OPT_NO_PAIR, OPT_TRI_SMALL, OPT_TRI_Q, OPT_NO_MR, OPT_MR_FORCE_BLUESTEIN, OPT_NO_ROWPQ,
   OPT_COLSOLVE, OPT_NO_LAT, OPT_F32_EPS_FLOOR, OPT_COLSTREAM_CHUNK, OPT_NO_ROWHALF, OPT_PAIR_MAXSIDE, OPT_ROWHALF_MINLG, OPT_NO_PQDCT,
-  OPT_NO_REORDER, OPT_NO_RAW, OPT_NO_TILEFUSE, OPT_NO_ROWPERS, OPT_NO_LFTILE, OPT_LF_ALL_ROUNDS, OPT_DFT_ENGINE, OPT_GAUSS_FFT_MINR, OPT_NO_GAUSS2D, OPT_NO_DFT_HALF, OPT_F32_STALL, OPT_PBS_LDS_PAD, OPT_NO_SHARED_PHASES, OPT_PA_STAG, OPT_PA_STAG_TICKS, OPT_PA_ROT, OPT_COUNT
+  OPT_NO_REORDER, OPT_NO_RAW, OPT_NO_TILEFUSE, OPT_NO_ROWPERS, OPT_NO_LFTILE, OPT_LF_ALL_ROUNDS, OPT_DFT_ENGINE, OPT_GAUSS_FFT_MINR, OPT_NO_GAUSS2D, OPT_NO_DFT_HALF, OPT_F32_STALL, OPT_PBS_LDS_PAD, OPT_NO_SHARED_PHASES, OPT_PA_STAG, OPT_PA_STAG_TICKS, OPT_PA_ROT, OPT_LF_STACK_BYTES, OPT_COUNT
 };
 struct OptVal {
   bool set;
@@ -298,6 +298,12 @@ hipError_t warp_invert_u(int dtype, const void* d_u, int n0, int n1, double scal
                          void* d_out, hipStream_t s, int mode, int nan_last, WarpWs* ws, const int* rects = nullptr, int nrect = 0);
 hipError_t warp_image(int dtype, const void* d_img, const void* d_uinv, int n0, int n1, void* d_out, hipStream_t s, WarpWs* ws,
                       const int* rects = nullptr, int nrect = 0);
+// undistort_image of B frames (B x n0 x n1) in chunks of warp_stack_chunk() frames.  per_frame == 0: one field d_u
+// (2 x n0 x n1) for all frames, inverted once into d_uinv (not null; d_u null: d_uinv already holds the inverse);
+// per_frame != 0: d_u is B x 2 x n0 x n1 and d_uinv (same layout) may be null.  The field that is undone is scale * u.
+int warp_stack_chunk(int dtype, int n0, int n1, int B, int per_frame);
+hipError_t warp_undistort_stack(int dtype, const void* d_frames, int B, const void* d_u, int per_frame, double scale, void* d_uinv,
+                                int n0, int n1, void* d_out, hipStream_t s, WarpWs* ws);
 // coefficients of an n0 x n1 f64 field for order-3 mode='constant' sampling (gpa_spline.h: interp_constant); d_tmp: n0 x n1
 hipError_t spline_coef_constant_f64(const double* d_in, int n0, int n1, double* d_tmp, double* d_out, hipStream_t s, WarpWs* ws);
 

@@ -33,13 +33,16 @@ constexpr int FR_OUT = 256 * FPT;      // outputs per workgroup (rows)
 // PADSRC: `in` is the UNPADDED sn0 x sn1 field and the m0 x m1 array this pass filters is its edge-replicated padding by npad
 // samples, scaled: element (x, y) = scale * in[clamp(x - npad)][clamp(y - npad)] is formed while the tile is loaded -- what
 // pad_edge_kernel used to write to memory and this kernel to read back (2 x 1.2 ms at 16384^2)
+// blockIdx.z: the plane of a stack (in_plane / out_plane elements apart; one plane: gridDim.z = 1)
 template <class T, bool PADSRC>
 __global__ __launch_bounds__(256) void fir_rows_kernel(const T* __restrict__ in, int m0, int m1, int ext,
                                                       const T* __restrict__ h, T* __restrict__ out, int npad, int sn0, int sn1,
-                                                      T scale) {
+                                                      T scale, size_t in_plane, size_t out_plane) {
   constexpr int KT = TapHalf<T>::value;
   __shared__ T tile[FR_OUT + 2 * KT];
   const int x = blockIdx.y, y0 = blockIdx.x * FR_OUT;
+  in += blockIdx.z * in_plane;
+  out += blockIdx.z * out_plane;
   if constexpr (PADSRC) {
     int sx = x - npad;
     sx = sx < 0 ? 0 : (sx >= sn0 ? sn0 - 1 : sx);
@@ -97,9 +100,11 @@ __global__ __launch_bounds__(256) void fir_rows_kernel(const T* __restrict__ in,
 // one column from a register window of 8 + 2 KT inputs (LDS column reads: conflict-free, 64 lanes = 64 banks)
 template <class T>
 __global__ __launch_bounds__(256) void fir_cols_kernel(const T* __restrict__ in, int m0, int m1, int ext,
-                                                      const T* __restrict__ h, T* __restrict__ out) {
+                                                      const T* __restrict__ h, T* __restrict__ out, size_t plane) {
   constexpr int KT = TapHalf<T>::value;
   __shared__ T tile[(32 + 2 * KT) * 64];
+  in += blockIdx.z * plane;      // (the plane of a stack, as in fir_rows_kernel)
+  out += blockIdx.z * plane;
   const int y0 = blockIdx.x * 64, x0 = blockIdx.y * 32;
   const int c = threadIdx.x & 63, g = threadIdx.x >> 6;
   const int yc = y0 + c < m1 ? y0 + c : m1 - 1;
@@ -175,10 +180,13 @@ __global__ __launch_bounds__(256) void invert_constant_kernel(const T* __restric
 template <class T, bool WIDE>
 __global__ __launch_bounds__(256) void invert_kernel(const T* __restrict__ c0, const T* __restrict__ c1, int m0, int m1,
                                                     int n0, int n1, int edge, int shift, int iters, T* __restrict__ out,
-                                                    int wr0, int wc0, int wc1, int all_rounds) {
+                                                    int wr0, int wc0, int wc1, int all_rounds, size_t cplane, size_t oplane) {
   const int o1 = n1 + 2 * edge, o0 = n0 + 2 * edge;
   const int j = wc0 + blockIdx.x * 256 + threadIdx.x, i = wr0 + blockIdx.y;
   if (j >= wc1) return;
+  c0 += blockIdx.z * cplane;     // blockIdx.z: the field of a stack (coefficients cplane, outputs oplane elements apart)
+  c1 += blockIdx.z * cplane;
+  out += blockIdx.z * oplane;
   const T* const coef[2] = {c0, c1};
   const T xb = T(i - edge + NPAD), yb = T(j - edge + NPAD);
   T v[2];
@@ -252,7 +260,11 @@ __device__ __forceinline__ bool interp_window(const T2<T>* __restrict__ win, int
 template <class T, bool WIDE>
 __global__ __launch_bounds__(256) void invert_tile_kernel(const T* __restrict__ c0, const T* __restrict__ c1, int m0, int m1,
                                                          int n0, int n1, int edge, int shift, int iters, T* __restrict__ out,
-                                                         int wr0, int wc0, int wr1, int wc1, int all_rounds) {
+                                                         int wr0, int wc0, int wr1, int wc1, int all_rounds, size_t cplane,
+                                                         size_t oplane) {
+  c0 += blockIdx.z * cplane;     // blockIdx.z: the field of a stack (coefficients cplane, outputs oplane elements apart)
+  c1 += blockIdx.z * cplane;
+  out += blockIdx.z * oplane;
   __shared__ T2<T> win[LW * LWP];
   __shared__ int box[4][4];                                // per wavefront: min x, min y, max x, max y of the first taps
   const int o1 = n1 + 2 * edge, o0 = n0 + 2 * edge;
@@ -366,6 +378,44 @@ __global__ __launch_bounds__(256) void warp_constant_kernel(const T* __restrict_
   out[o] = r[0];
 }
 
+// The same resampling for a STACK of frames (coefficient planes and output planes npx elements apart).  One thread is one
+// pixel: its coordinate r + u_inv(r) and the 4 + 4 spline weights do not depend on the frame, so interp_constant evaluates
+// them once per pass of NF frames (and the compiler hoists them out of the loop over the passes: they are loop-invariant),
+// and every tap address is shared by the NF gathers of a pass.  A workgroup row (blockIdx.z) takes `per` consecutive
+// frames, a multiple of NF; the frames left over at the end of the stack go one at a time.  NF = 4: 157 VGPRs in f64 (202 with
+// 64-bit tap offsets), 111 in f32, no scratch (tools/kernel_resources.py gpa_warp) -- three f64 wavefronts per SIMD.
+// uinv_plane != 0: every frame has its own u_inv (uinv_plane elements apart) -- the NF = 1 form with per = 1, the frame
+// from blockIdx.z.  The sums per output are interp_constant's whatever NF is: the bits of warp_constant_kernel.
+constexpr int WARP_NF = 4;
+template <class T, int NF, bool WIDE>
+__global__ __launch_bounds__(256) void warp_stack_kernel(const T* __restrict__ coef, int n0, int n1, const T* __restrict__ uinv,
+                                                        size_t uinv_plane, T cval, T* __restrict__ out, int nfr, int per) {
+  const int j = blockIdx.x * 256 + threadIdx.x, i = blockIdx.y;
+  if (j >= n1) return;
+  const size_t o = (size_t)i * n1 + j, npx = (size_t)n0 * n1;
+  int f = blockIdx.z * per;
+  const int f1 = f + per < nfr ? f + per : nfr;
+  uinv += blockIdx.z * uinv_plane;
+  const T x = T(i) + uinv[o], y = T(j) + uinv[npx + o];
+  if constexpr (NF > 1) {
+    for (; f + NF <= f1; f += NF) {
+      const T* cf[NF];
+#pragma unroll
+      for (int n = 0; n < NF; ++n) cf[n] = coef + (size_t)(f + n) * npx;
+      T r[NF];
+      interp_constant<T, NF, WIDE>(cf, n0, n1, x, y, cval, r);
+#pragma unroll
+      for (int n = 0; n < NF; ++n) out[(size_t)(f + n) * npx + o] = r[n];
+    }
+  }
+  for (; f < f1; ++f) {
+    const T* const cf[1] = {coef + (size_t)f * npx};
+    T r[1];
+    interp_constant<T, 1, WIDE>(cf, n0, n1, x, y, cval, r);
+    out[(size_t)f * npx + o] = r[0];
+  }
+}
+
 // the prefilter's taps, uploaded once per workspace and precision (pinned staging is not worth it: 65 values)
 template <class T>
 hipError_t ensure_taps(WarpWs* ws, hipStream_t s) {
@@ -401,18 +451,21 @@ hipError_t reserve(WarpWs* ws, size_t bytes, hipStream_t s) {
 
 // coefficients of `in` (m0 x m1); tmp: same size.  npad >= 0: `in` is the unpadded (m0 - 2 npad) x (m1 - 2 npad) field, padded
 // by edge replication and scaled on the fly (fir_rows_kernel<PADSRC>)
+// planes > 1: a stack -- `in` holds planes of in_plane elements (the unpadded size when npad >= 0), tmp and out planes of
+// m0 x m1 (planes <= 65535: gridDim.z)
 template <class T>
 hipError_t prefilter(const T* in, int m0, int m1, int ext, const T* d_h, T* tmp, T* out, hipStream_t s, int npad = -1,
-                     T scale = T(1)) {
+                     T scale = T(1), int planes = 1, size_t in_plane = 0) {
+  const size_t mp = (size_t)m0 * m1;
   {
     GPA_PROF("fir_rows_kernel", s);
-    const dim3 grid((m1 + FR_OUT - 1) / FR_OUT, m0);
-    if (npad >= 0) fir_rows_kernel<T, true><<<grid, 256, 0, s>>>(in, m0, m1, ext, d_h, tmp, npad, m0 - 2 * npad, m1 - 2 * npad, scale);
-    else fir_rows_kernel<T, false><<<grid, 256, 0, s>>>(in, m0, m1, ext, d_h, tmp, 0, m0, m1, T(1));
+    const dim3 grid((m1 + FR_OUT - 1) / FR_OUT, m0, planes);
+    if (npad >= 0) fir_rows_kernel<T, true><<<grid, 256, 0, s>>>(in, m0, m1, ext, d_h, tmp, npad, m0 - 2 * npad, m1 - 2 * npad, scale, in_plane, mp);
+    else fir_rows_kernel<T, false><<<grid, 256, 0, s>>>(in, m0, m1, ext, d_h, tmp, 0, m0, m1, T(1), in_plane, mp);
   }
   {
     GPA_PROF("fir_cols_kernel", s);
-    fir_cols_kernel<T><<<dim3((m1 + 63) / 64, (m0 + 31) / 32), 256, 0, s>>>(tmp, m0, m1, ext, d_h, out);
+    fir_cols_kernel<T><<<dim3((m1 + 63) / 64, (m0 + 31) / 32, planes), 256, 0, s>>>(tmp, m0, m1, ext, d_h, out, mp);
   }
   return hipGetLastError();
 }
@@ -464,6 +517,33 @@ hipError_t invert_constant_t(const T* d_u, int n0, int n1, T scale, int iters, i
   return e;
 }
 
+// the fixed-point rounds of mode 'nearest' on the coefficients c0, c1 (m0 x m1 each) of nfr fields: field f reads its
+// coefficients cplane elements and writes its output oplane elements behind field f - 1's (nfr <= 65535: gridDim.z)
+template <class T>
+hipError_t launch_invert(const T* c0, const T* c1, size_t cplane, int m0, int m1, int n0, int n1, int edge, int shift, int iters,
+                         T* d_out, size_t oplane, int nfr, hipStream_t s, const int* rects, int nrect) {
+  const size_t mp = (size_t)m0 * m1;
+  const int o1 = n1 + 2 * edge, o0 = n0 + 2 * edge;
+  const int allr = opt_set(OPT_LF_ALL_ROUNDS) ? 1 : 0;   // (diagnostic: every round of the fixed point, no early exit)
+  for (int q = 0; q < (nrect > 0 ? nrect : 1); ++q) {
+    const Win v = window(nrect > 0 ? rects + 4 * q : nullptr, o0, o1);
+    if (v.h <= 0 || v.w <= 0) continue;
+    GPA_PROF("invert_kernel", s);
+    if (!opt_set(OPT_NO_LFTILE)) {
+      // 16 x 16 tiles, the later rounds from an LDS window (NO_LFTILE: the row-segment kernel, every round from L1 / L2)
+      const dim3 grid((v.w + LT - 1) / LT, (v.h + LT - 1) / LT, nfr);
+      if (mp * sizeof(T) < ((size_t)1 << 32))
+        invert_tile_kernel<T, false><<<grid, 256, 0, s>>>(c0, c1, m0, m1, n0, n1, edge, shift, iters, d_out, v.r0, v.c0, v.r0 + v.h, v.c0 + v.w, allr, cplane, oplane);
+      else
+        invert_tile_kernel<T, true><<<grid, 256, 0, s>>>(c0, c1, m0, m1, n0, n1, edge, shift, iters, d_out, v.r0, v.c0, v.r0 + v.h, v.c0 + v.w, allr, cplane, oplane);
+    } else if (mp * sizeof(T) < ((size_t)1 << 32))
+      invert_kernel<T, false><<<dim3((v.w + 255) / 256, v.h, nfr), 256, 0, s>>>(c0, c1, m0, m1, n0, n1, edge, shift, iters, d_out, v.r0, v.c0, v.c0 + v.w, allr, cplane, oplane);
+    else
+      invert_kernel<T, true><<<dim3((v.w + 255) / 256, v.h, nfr), 256, 0, s>>>(c0, c1, m0, m1, n0, n1, edge, shift, iters, d_out, v.r0, v.c0, v.c0 + v.w, allr, cplane, oplane);
+  }
+  return hipGetLastError();
+}
+
 template <class T>
 hipError_t invert_t(const T* d_u, int n0, int n1, T scale, int iters, int edge, int shift, T* d_out, hipStream_t s, WarpWs* ws,
                     const int* rects, int nrect) {
@@ -478,27 +558,7 @@ hipError_t invert_t(const T* d_u, int n0, int n1, T scale, int iters, int edge, 
   // (scaling and the 12-sample edge padding of mode 'nearest' happen while the row pass loads its tiles)
   for (int c = 0; c < 2 && e == hipSuccess; ++c)
     e = prefilter<T>(d_u + (size_t)c * n0 * n1, m0, m1, EXT_REFLECT, d_h, tmp, c == 0 ? c0 : c1, s, NPAD, scale);
-  if (e == hipSuccess) {
-    const int o1 = n1 + 2 * edge, o0 = n0 + 2 * edge;
-    const int allr = opt_set(OPT_LF_ALL_ROUNDS) ? 1 : 0;   // (diagnostic: every round of the fixed point, no early exit)
-    for (int q = 0; q < (nrect > 0 ? nrect : 1); ++q) {
-      const Win v = window(nrect > 0 ? rects + 4 * q : nullptr, o0, o1);
-      if (v.h <= 0 || v.w <= 0) continue;
-      GPA_PROF("invert_kernel", s);
-      if (!opt_set(OPT_NO_LFTILE)) {
-        // 16 x 16 tiles, the later rounds from an LDS window (NO_LFTILE: the row-segment kernel, every round from L1 / L2)
-        const dim3 grid((v.w + LT - 1) / LT, (v.h + LT - 1) / LT);
-        if (mp * sizeof(T) < ((size_t)1 << 32))
-          invert_tile_kernel<T, false><<<grid, 256, 0, s>>>(c0, c1, m0, m1, n0, n1, edge, shift, iters, d_out, v.r0, v.c0, v.r0 + v.h, v.c0 + v.w, allr);
-        else
-          invert_tile_kernel<T, true><<<grid, 256, 0, s>>>(c0, c1, m0, m1, n0, n1, edge, shift, iters, d_out, v.r0, v.c0, v.r0 + v.h, v.c0 + v.w, allr);
-      } else if (mp * sizeof(T) < ((size_t)1 << 32))
-        invert_kernel<T, false><<<dim3((v.w + 255) / 256, v.h), 256, 0, s>>>(c0, c1, m0, m1, n0, n1, edge, shift, iters, d_out, v.r0, v.c0, v.c0 + v.w, allr);
-      else
-        invert_kernel<T, true><<<dim3((v.w + 255) / 256, v.h), 256, 0, s>>>(c0, c1, m0, m1, n0, n1, edge, shift, iters, d_out, v.r0, v.c0, v.c0 + v.w, allr);
-    }
-    e = hipGetLastError();
-  }
+  if (e == hipSuccess) e = launch_invert<T>(c0, c1, 0, m0, m1, n0, n1, edge, shift, iters, d_out, 0, 1, s, rects, nrect);
   return e;
 }
 
@@ -529,7 +589,103 @@ hipError_t warp_t(const T* d_img, const T* d_uinv, int n0, int n1, T* d_out, hip
   return e;
 }
 
+// ---- undistort_image of a stack of frames -----------------------------------------------------------------------------
+// The frames go through the scratch in chunks: a chunk's spline planes, not the stack's, live in the workspace.  The chunk
+// is the number of frames whose planes fit WARP_STACK_BYTES (option LF_STACK_BYTES: another bound, for tests), at least
+// one frame -- the scratch of a single frame is the floor, as for undistort_image -- and at most 32767 (two field planes
+// per frame in gridDim.z).  Elements of scratch per frame of a chunk: shared field -- the rows-filtered frame and its
+// coefficients; fields per frame -- rows-filtered and coefficient planes of both padded components, the frame's u_inv, and the
+// frame's coefficients (its rows-filtered plane reuses the components').
+constexpr size_t WARP_STACK_BYTES = (size_t)512 << 20;
+inline size_t stack_frame_elems(int n0, int n1, int per_frame) {
+  const size_t npx = (size_t)n0 * n1, mp = (size_t)(n0 + 2 * NPAD) * (n1 + 2 * NPAD);
+  return per_frame ? 4 * mp + 3 * npx : 2 * npx;
+}
+inline int stack_chunk(size_t rs, int n0, int n1, int B, int per_frame) {
+  size_t bound = WARP_STACK_BYTES;
+  if (opt_set(OPT_LF_STACK_BYTES) && opt(OPT_LF_STACK_BYTES).num >= 1.0) bound = (size_t)opt(OPT_LF_STACK_BYTES).num;
+  size_t c = bound / (stack_frame_elems(n0, n1, per_frame) * rs);
+  if (c < 1) c = 1;
+  if (c > 32767) c = 32767;
+  return c < (size_t)B ? (int)c : B;
+}
+// bytes of the single inversion that precedes the chunks of a shared field (invert_t's region, in front of theirs)
+inline size_t stack_lead_bytes(size_t rs, int n0, int n1, int per_frame) {
+  return per_frame ? 0 : 4 * (size_t)(n0 + 2 * NPAD) * (n1 + 2 * NPAD) * rs;
+}
+
+template <class T>
+hipError_t resample_stack(const T* coef, const T* uinv, int per_frame, int n0, int n1, T* out, int nfr, hipStream_t s) {
+  const size_t npx = (size_t)n0 * n1;
+  const bool wide = npx * sizeof(T) >= ((size_t)1 << 32);
+  GPA_PROF("warp_stack_kernel", s);
+  if (per_frame) {
+    const dim3 grid((n1 + 255) / 256, n0, nfr);
+    if (!wide) warp_stack_kernel<T, 1, false><<<grid, 256, 0, s>>>(coef, n0, n1, uinv, 2 * npx, T(0), out, nfr, 1);
+    else warp_stack_kernel<T, 1, true><<<grid, 256, 0, s>>>(coef, n0, n1, uinv, 2 * npx, T(0), out, nfr, 1);
+  } else {
+    // enough workgroups to fill the device (~16 per compute unit) before a thread takes more than one pass of frames
+    const long long wg = (long long)((n1 + 255) / 256) * n0;
+    long long gz = (16LL * device_cus() + wg - 1) / wg;
+    const int passes = (nfr + WARP_NF - 1) / WARP_NF;
+    if (gz > passes) gz = passes;
+    if (gz < 1) gz = 1;
+    const int per = (int)((passes + gz - 1) / gz) * WARP_NF;
+    const dim3 grid((n1 + 255) / 256, n0, (nfr + per - 1) / per);
+    if (!wide) warp_stack_kernel<T, WARP_NF, false><<<grid, 256, 0, s>>>(coef, n0, n1, uinv, 0, T(0), out, nfr, per);
+    else warp_stack_kernel<T, WARP_NF, true><<<grid, 256, 0, s>>>(coef, n0, n1, uinv, 0, T(0), out, nfr, per);
+  }
+  return hipGetLastError();
+}
+
+template <class T>
+hipError_t undistort_stack_t(const T* d_frames, int B, const T* d_u, int per_frame, T scale, T* d_uinv, int n0, int n1, T* d_out,
+                             hipStream_t s, WarpWs* ws) {
+  const int m0 = n0 + 2 * NPAD, m1 = n1 + 2 * NPAD;
+  const size_t npx = (size_t)n0 * n1, mp = (size_t)m0 * m1;
+  const int chunk = stack_chunk(sizeof(T), n0, n1, B, per_frame);
+  const size_t lead = stack_lead_bytes(sizeof(T), n0, n1, per_frame);
+  // ONE reservation for the inversion and the chunks (the inversion's own reserve() then finds the scratch large enough)
+  hipError_t e = reserve(ws, lead + (size_t)chunk * stack_frame_elems(n0, n1, per_frame) * sizeof(T), s);
+  if (e == hipSuccess) e = ensure_taps<T>(ws, s);
+  if (e != hipSuccess) return e;
+  const T* d_h = (const T*)ws->taps;
+  T* buf = (T*)((char*)ws->buf + lead);
+  if (!per_frame) {
+    // one field for all frames: inverted ONCE, as undistort_image inverts it (35 rounds, mode 'nearest', no edge)
+    if (d_u) e = invert_t<T>(d_u, n0, n1, -scale, 35, 0, 0, d_uinv, s, ws, nullptr, 0);
+    T *tmp = buf, *coef = buf + (size_t)chunk * npx;
+    for (int f0 = 0; f0 < B && e == hipSuccess; f0 += chunk) {
+      const int nb = B - f0 < chunk ? B - f0 : chunk;
+      e = prefilter<T>(d_frames + (size_t)f0 * npx, n0, n1, EXT_MIRROR, d_h, tmp, coef, s, -1, T(1), nb, npx);
+      if (e == hipSuccess) e = resample_stack<T>(coef, d_uinv, 0, n0, n1, d_out + (size_t)f0 * npx, nb, s);
+    }
+    return e;
+  }
+  T *tmp = buf, *fcoef = buf + 2 * (size_t)chunk * mp, *uscr = buf + 4 * (size_t)chunk * mp, *coef = uscr + 2 * (size_t)chunk * npx;
+  for (int f0 = 0; f0 < B && e == hipSuccess; f0 += chunk) {
+    const int nb = B - f0 < chunk ? B - f0 : chunk;
+    T* uinv = d_uinv ? d_uinv + 2 * (size_t)f0 * npx : uscr;
+    // the 2 nb components of the chunk's fields in one prefilter (plane 2 f + c), the nb inversions in one launch
+    e = prefilter<T>(d_u + 2 * (size_t)f0 * npx, m0, m1, EXT_REFLECT, d_h, tmp, fcoef, s, NPAD, -scale, 2 * nb, npx);
+    if (e == hipSuccess) e = launch_invert<T>(fcoef, fcoef + mp, 2 * mp, m0, m1, n0, n1, 0, 0, 35, uinv, 2 * npx, nb, s, nullptr, 0);
+    if (e == hipSuccess) e = prefilter<T>(d_frames + (size_t)f0 * npx, n0, n1, EXT_MIRROR, d_h, tmp, coef, s, -1, T(1), nb, npx);
+    if (e == hipSuccess) e = resample_stack<T>(coef, uinv, 1, n0, n1, d_out + (size_t)f0 * npx, nb, s);
+  }
+  return e;
+}
+
 }  // namespace
+
+int warp_stack_chunk(int dtype, int n0, int n1, int B, int per_frame) {
+  return stack_chunk(dtype == 0 ? 4 : 8, n0, n1, B, per_frame);
+}
+
+hipError_t warp_undistort_stack(int dtype, const void* d_frames, int B, const void* d_u, int per_frame, double scale, void* d_uinv,
+                                int n0, int n1, void* d_out, hipStream_t s, WarpWs* ws) {
+  return dtype == 0 ? undistort_stack_t<float>((const float*)d_frames, B, (const float*)d_u, per_frame, (float)scale, (float*)d_uinv, n0, n1, (float*)d_out, s, ws)
+                    : undistort_stack_t<double>((const double*)d_frames, B, (const double*)d_u, per_frame, scale, (double*)d_uinv, n0, n1, (double*)d_out, s, ws);
+}
 
 hipError_t warp_reserve_undistort(int dtype, int n0, int n1, WarpWs* ws, hipStream_t s) {
   const size_t rs = dtype == 0 ? 4 : 8;

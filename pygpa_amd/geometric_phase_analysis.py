@@ -607,3 +607,17 @@ def undistort_image(deformed, u, dtype=None):
     deformed = np.asarray(deformed)
     plan = _lib.get_plan(deformed.shape, 1, DEFAULT_DTYPE if dtype is None else dtype)
     return plan.undistort_image(deformed, u)
+
+
+def undistort_image_stack(frames, u, dtype=None):
+    """`undistort_image` of every frame of a stack `frames` (B, N, M) -- a movie, a tilt or temperature series -- in one
+    device call.  `u` has the sign convention of `undistort_image` and is either (2, N, M), ONE field for all frames (a
+    static detector distortion): it is prefiltered and inverted once and the spline weights of a pixel serve every frame;
+    or (B, 2, N, M), a field per frame (minus what `extract_displacement_field_stack` returns): the B inversions share one
+    set of kernel launches.  No counterpart in the reference, where a Python loop over `undistort_image`
+    (geometric_phase_analysis.py:935-974) gives the same numbers; frame b equals `undistort_image(frames[b], u)`
+    (or `u[b]`) bit for bit.  Returns (B, N, M)."""
+    frames, u = np.asarray(frames), np.asarray(u)
+    _lib.stack_shapes(frames.shape, u.shape)      # ValueError before a plan (and with it the library) is touched
+    plan = _lib.get_plan(frames.shape[1:], 1, DEFAULT_DTYPE if dtype is None else dtype)
+    return plan.undistort_image_stack(frames, u)
