@@ -23,8 +23,8 @@ static int check_ranges(gpa_plan* p, const std::string& fn, int P, int K, int km
 
 // host-side preparation: filter / carrier / k-matrix tables (re-staged only when they change; these upload
 // synchronously), the x-plane buffer, and the second unwrap workspace + stream
-static int extract_stage(gpa_plan* p, const double* kvecs, int P, const double* klists, int K, double sigma, int* Bx) {
-  TRY(stage_sweep(p, kvecs, P, klists, K, sigma, Bx));
+static int extract_stage(gpa_plan* p, const double* kvecs, int P, const double* klists, int K, double sigma, int* Bx, int passb) {
+  TRY(stage_sweep(p, kvecs, P, klists, K, sigma, Bx, passb));
   TRY(stage_kmat(p, kvecs, P));
   {
     // (PAIR_MAXSIDE: measurement switch for the size up to which both components share one set of launches)
@@ -149,7 +149,7 @@ static int extract_enqueue(gpa_plan* p, const char* what, const void* image, con
   if (o.grads && (o.grad_mode < 0 || o.grad_mode > 2)) return fail(GPA_ERR_ARG, fn + ": grad_mode must be 0, 1 or 2");
   HIP_TRY(hipSetDevice(p->device));
   int Bx = 0;
-  TRY(extract_stage(p, kvecs, P, klists, K, sigma, &Bx));
+  TRY(extract_stage(p, kvecs, P, klists, K, sigma, &Bx, o.grads ? SWEEP_PASSB_PHASES : SWEEP_PASSB_SELECT));
   // the phases of all P K candidates (reals): allocated by the first call that asks for gradients, kept by the plan
   if (o.grads) TRY(ensure_sf(p, (size_t)P * K * p->n0 * p->n1 * p->rsz));
   // per-kernel event pairs while profiling (installed for this thread until the function returns)
@@ -334,7 +334,7 @@ int gpa_extract_displacement_field_batch_dev(gpa_plan* p, const void* images, in
   TRY(check_ranges(p, fn, P, K, kmax));
   HIP_TRY(hipSetDevice(p->device));
   int Bx = 0;
-  TRY(extract_stage(p, kvecs, P, klists, K, sigma, &Bx));
+  TRY(extract_stage(p, kvecs, P, klists, K, sigma, &Bx, SWEEP_PASSB_SELECT));
   TRY(ensure_batch_unwrap(p, B));
   const size_t npx = (size_t)p->n0 * p->n1;
   // the sweep and the least squares of a chunk of images are ONE set of launches too (blockIdx.z / .y = image);

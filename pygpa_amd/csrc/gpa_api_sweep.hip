@@ -34,8 +34,18 @@ int gpa_lockin_batch(gpa_plan* p, const void* image, const double* kvecs, int B,
 // host-side staging of a sweep of P peaks with K candidates each (klists: P x K x 2; every candidate of peak p is compensated
 // to krefs[p]): filter tables of this sigma, candidate / reference lists and carrier tables (re-staged only when they change;
 // these upload synchronously), room for the x-planes; their number comes back in *Bx
-int stage_sweep(gpa_plan* p, const double* krefs, int P, const double* klists, int K, double sigma, int* Bx) {
+// Does pass B of the sweep being staged take the shared-forward kernel?  The one place that decides: passB_select and
+// passB_phases ask it again after pass A.
+static bool shared_passB_runs(const gpa_plan* p, int passb) {
+  if (!p->sh_use) return false;
+  const bool phases_ok = p->use_shared && !opt_set(OPT_NO_SHARED_PHASES) && p->sh_one_kref;
+  if (passb == SWEEP_PASSB_SELECT) return true;
+  return passb == SWEEP_PASSB_PHASES && phases_ok;
+}
+
+int stage_sweep(gpa_plan* p, const double* krefs, int P, const double* klists, int K, double sigma, int* Bx, int passb) {
   const int B = P * K;
+  p->ys_use = false;
   TRY(ensure_filters(p, sigma));
   std::vector<double> kr((size_t)B * 2);
   for (int pp = 0; pp < P; ++pp)
@@ -44,11 +54,24 @@ int stage_sweep(gpa_plan* p, const double* krefs, int P, const double* klists, i
       kr[2 * ((size_t)pp * K + k) + 1] = krefs[2 * pp + 1];
     }
   TRY(stage_kvectors(p, klists, kr.data(), B, Bx));
-  return ensure_tbuf(p, *Bx);
+  TRY(ensure_tbuf(p, *Bx));
+  if (passb != SWEEP_PASSB_OTHER) {
+    // the path of the whole sweep is chosen here, before pass A: the y-spectral one where the shared-forward pass B will run
+    // on periodic rows of 2048 / 4096 points with a rotated band (a single image and a stack stage alike: same path)
+    TRY(shared_prepare(p, P, K));
+    p->ys_use = shared_passB_runs(p, passb) && p->ys_ok && !opt_set(OPT_NO_YSPEC);
+    if (p->ys_use) TRY(ensure_yspec(p, 1, *Bx));
+  }
+  return GPA_OK;
 }
 
 // pass A over the staged x-planes (per-plane forward transforms, the image tile kept in registers)
 int run_passA(gpa_plan* p, const void* image, const void* mean, void* Tbuf, int Bx, int nimg) {
+  if (p->ys_use) {
+    TRY(ensure_yspec(p, nimg, Bx));   // (a stack: room for its images; a single image has it from staging)
+    HIP_TRY(launch_passA_yspec(p->dtype, p->ax0, p->ax1, image, mean, p->tb, p->Hx, p->tw0, p->tw1, Tbuf, Bx, p->ys, p->stream, nimg));
+    return GPA_OK;
+  }
   HIP_TRY(launch_passA(p->dtype, p->ax0, p->n1, image, mean, p->tb, p->Hx, p->tw0, Tbuf, Bx, p->stream, nimg));
   return GPA_OK;
 }
@@ -67,13 +90,18 @@ int passB_select(gpa_plan* p, const XPlanes& xp, int P, int K, void* lockin, int
   //  measured slower -- 153 -> 188 us -- because the merge pass and the partial slabs cost more than they save)
   if (xp.stride == 0 && p->ax1.lg <= 10 && K >= 4 && !p->no_ksplit && rows_wg <= 256)
     while (ksplit < 4 && ksplit * 2 <= K && rows_wg * ksplit < 1024) ksplit *= 2;
+  const bool ys = p->ys_use;   // (shared_prepare clears it: the planes pass A left are what they are)
+  if (ys && ksplit != 1) return fail(GPA_ERR_STATE, "pass B: the staged sweep took the y-spectral pass A");
   if (ksplit == 1) {
     TRY(shared_prepare(p, P, K));
+    p->ys_use = ys;
+    if (ys && !p->sh_use) return fail(GPA_ERR_STATE, "pass B: the staged sweep took the y-spectral pass A");
     if (p->sh_use) {
       p->lk_raw = raw && !opt_set(OPT_NO_RAW) && p->sh_one_kref;
+      const PassBYspec yb = {p->ys.strips, p->d_shifts};
       HIP_TRY(launch_passB_shared(p->dtype, p->ax1s, p->n0, xp.T, p->ax1s.L == p->ax1.L ? p->tw1 : p->tw1s, p->tb,
                                   p->sh, p->sh_E, p->sh_Epad, P, K, lockin, kidx, p->stream, xp.nimg, xp.stride, p->sh_nbl,
-                                  p->lk_raw));
+                                  p->lk_raw, ys ? &yb : nullptr));
     } else
       HIP_TRY(launch_passB(p->dtype, p->ax1, p->n0, xp.T, p->Hy, p->tw1, p->tb, P, K, true, lockin, kidx, p->stream, xp.nimg,
                            xp.stride));
@@ -95,19 +123,24 @@ int passB_select(gpa_plan* p, const XPlanes& xp, int P, int K, void* lockin, int
 int passB_phases(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, void* psi, bool* shared) {
   p->lk_raw = false;
   *shared = false;
+  const bool ys = p->ys_use;   // (shared_prepare clears it: the planes pass A left are what they are)
   if (p->use_shared && !opt_set(OPT_NO_SHARED_PHASES)) {
     TRY(shared_prepare(p, P, K));
+    p->ys_use = ys;
     if (p->sh_use && p->sh_one_kref) {
+      const PassBYspec yb = {p->ys.strips, p->d_shifts};
       const hipError_t e = launch_passB_shared_phases(p->dtype, p->ax1s, p->n0, p->Tbuf, p->ax1s.L == p->ax1.L ? p->tw1 : p->tw1s,
                                                       p->tb, p->sh, p->sh_E, p->sh_Epad, P, K, lockin, kidx, psi, p->stream, 0,
-                                                      p->sh_nbl);
+                                                      p->sh_nbl, ys ? &yb : nullptr);
       if (e == hipSuccess) {
         *shared = true;
         return GPA_OK;
       }
-      if (e != hipErrorInvalidValue) return fail(GPA_ERR_HIP, std::string("shared pass B (phases): ") + hipGetErrorString(e));
+      if (e != hipErrorInvalidValue || ys) return fail(GPA_ERR_HIP, std::string("shared pass B (phases): ") + hipGetErrorString(e));
     }
   }
+  // (the per-candidate kernel reads spatial x-planes)
+  if (ys) return fail(GPA_ERR_STATE, "pass B (phases): the staged sweep took the y-spectral pass A");
   HIP_TRY(launch_passB_ext(p->dtype, p->ax1, p->n0, p->Tbuf, p->Hy, p->tw1, p->tb, K, 3, lockin, kidx, nullptr, psi, p->stream, P));
   return GPA_OK;
 }
@@ -140,7 +173,7 @@ int sweep_peaks_dev(gpa_plan* p, const void* image, const void* mean, const doub
                            const double* klists, int K, double sigma, void* lockin, int32_t* kidx, bool raw) {
   if (P * K > p->max_batch) return fail(GPA_ERR_STATE, "sweep: P*K exceeds the plan's max_batch");
   int Bx = 0;
-  TRY(stage_sweep(p, krefs, P, klists, K, sigma, &Bx));
+  TRY(stage_sweep(p, krefs, P, klists, K, sigma, &Bx, SWEEP_PASSB_SELECT));
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[1], p->stream));
   TRY(run_passA(p, image, mean, p->Tbuf, Bx, 1));
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[2], p->stream));
@@ -177,7 +210,7 @@ int gpa_sweep_grad_dev(gpa_plan* p, const void* image, const double* kref, const
   TRY(ensure_sf(p, (size_t)K * npx * p->rsz));
   int32_t* ki = kidx ? kidx : p->d_kidx;
   int Bx = 0;
-  TRY(stage_sweep(p, kref, 1, klist, K, sigma, &Bx));
+  TRY(stage_sweep(p, kref, 1, klist, K, sigma, &Bx, SWEEP_PASSB_PHASES));
   TRY(run_passA(p, image, nullptr, p->Tbuf, Bx, 1));
   // rows the shared-forward pass B takes (2048- / 4096- / f32 8192-point classes, lists with runs on their x-planes): one
   // forward transform per x-plane row instead of one per candidate, the phases written by that kernel (round 6; NO_SHARED or

@@ -203,6 +203,7 @@ int ensure_filters(gpa_plan* p, double sigma) {
 // or the list changed.  Leaves p->sh_use = whether pass B should take that kernel for this (P, K).
 int shared_prepare(gpa_plan* p, int P, int K) {
   p->sh_use = false;
+  p->ys_use = false;
   const int B = P * K;
   if (!p->sh_ok || !p->use_shared || K < 2 || (int)p->staged_planeof.size() < B) return GPA_OK;
   const bool reorder = !opt_set(OPT_NO_REORDER);
@@ -363,6 +364,35 @@ int shared_prepare(gpa_plan* p, int P, int K) {
   HIP_TRY(launch_shared_tables(p->dtype, p->ax1s, p->d_wys, p->d_kr, p->d_shifts, p->d_taps, p->sh_etab, p->sh_E, p->sh_Epad, B, K,
                                p->sh_nbl, p->sh, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));   // `desc`, `order` are locals
+  // y-spectral sweep: which blocks of n1 / 16 stored positions of every x-plane's spectrum pass B will read -- the union, over the
+  // peaks whose candidates use the plane, of the blocks their band rotation selects (yspec_blockmask) -- as a list of
+  // (plane, block) pairs for pass A.  The list is dealt by block slot, so that neighbouring entries are different planes.
+  p->ys_ok = false;
+  if (passB_yspec_supports(p->dtype, p->ax1s, p->sh_nbl) && p->ax1s.L == p->ax1.L && !p->ax1.padded) {
+    const int nplanes = p->last_planes;
+    std::vector<unsigned> mask((size_t)nplanes, 0u);
+    for (int b = 0; b < B; ++b) mask[p->staged_planeof[b]] |= yspec_blockmask(p->ax1s.lg, shifts[b / K], p->sh_nbl);
+    std::vector<int> pairs;
+    unsigned all = 0;
+    for (int slot = 0; slot < 16; ++slot)
+      for (int q = 0; q < nplanes; ++q) {
+        int seen = 0;
+        for (int blk = 0; blk < 16; ++blk)
+          if ((mask[q] >> blk) & 1) {
+            if (seen++ == slot) pairs.push_back(q | (blk << 16));
+          }
+        all |= mask[q];
+      }
+    if (!p->d_ys_pairs) TRY(dmalloc(p, (void**)&p->d_ys_pairs, (size_t)p->max_batch * 16 * sizeof(int)));
+    HIP_TRY(hipMemcpyAsync(p->d_ys_pairs, pairs.data(), pairs.size() * sizeof(int), hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));   // `pairs` is a local
+    p->ys.pairs = p->d_ys_pairs;
+    p->ys.npairs = (int)pairs.size();
+    p->ys.blockmask = all;
+    p->ys.E = p->sh_E;
+    p->ys.Epad = p->sh_Epad;
+    p->ys_ok = !pairs.empty();
+  }
   p->sh_built_epoch = p->sh_epoch;
   p->sh_built_K = K;
   p->sh_built_B = B;
@@ -375,6 +405,7 @@ int shared_prepare(gpa_plan* p, int P, int K) {
 // x-planes (one per distinct wx, see SweepTables) and build the carrier tables.
 // Returns the number of x-planes in *planes_out.
 int stage_kvectors(gpa_plan* p, const double* kl, const double* kr_per_b, int B, int* planes_out) {
+  p->ys_use = false;   // (the y-spectral path is chosen per staged sweep: stage_sweep)
   // same candidates as the previous call (a sequence of images analysed with one k-list):
   // the carrier tables on the device are still valid, nothing to copy and nothing to wait for
   if ((int)p->staged_kl.size() == 2 * B && memcmp(p->staged_kl.data(), kl, (size_t)B * 2 * sizeof(double)) == 0 &&
@@ -425,6 +456,24 @@ int ensure_tbuf(gpa_plan* p, int planes) {
   p->tbuf_planes = 0;
   TRY(dmalloc(p, &p->Tbuf, (size_t)planes * npx * p->csz));
   p->tbuf_planes = planes;
+  return GPA_OK;
+}
+
+// Yhat and the end strips of the y-spectral sweep for nimg images of Bx planes
+int ensure_yspec(gpa_plan* p, int nimg, int Bx) {
+  const size_t yb = (size_t)nimg * p->n0 * p->n1 * p->csz, sb = (size_t)nimg * Bx * p->n0 * 2 * p->sh_Epad * p->csz;
+  if (yb > p->ys_yhat_bytes) {
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (p->ys.Yhat) { HIP_TRY(hipFree(p->ys.Yhat)); p->ws_bytes -= p->ys_yhat_bytes; p->ys.Yhat = nullptr; p->ys_yhat_bytes = 0; }
+    TRY(dmalloc(p, &p->ys.Yhat, yb));
+    p->ys_yhat_bytes = yb;
+  }
+  if (sb > p->ys_strips_bytes) {
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (p->ys.strips) { HIP_TRY(hipFree(p->ys.strips)); p->ws_bytes -= p->ys_strips_bytes; p->ys.strips = nullptr; p->ys_strips_bytes = 0; }
+    TRY(dmalloc(p, &p->ys.strips, sb));
+    p->ys_strips_bytes = sb;
+  }
   return GPA_OK;
 }
 

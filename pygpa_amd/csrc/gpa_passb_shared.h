@@ -38,13 +38,20 @@ hipError_t launch_shared_tables(int dtype, const Axis& a1, const double* wys, co
                                 hipStream_t s);
 int passB_shared_nbl(int dtype, int need);
 
+// ys != null: the y-spectral form -- Tbuf holds FFT_y of the x-planes in the spectral register layout (pass A on
+// spectrum columns, launch_passA_yspec) and the kernel runs no forward transform; strips: [image][plane][n0][2 Epad] complex,
+// the spatial samples within Epad of either row end; shifts: device [P], the band rotation of every peak
+struct PassBYspec { const void* strips; const int* shifts; };
+bool passB_yspec_supports(int dtype, const Axis& a1, int nbl);
+
 // a1: the shared kernel's own geometry of the y axis (periodic, or zero-padded to L >= n + E); tw1: twiddles of a1.L
 hipError_t launch_passB_shared(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* tw1, const SweepTables& tb,
                                const PassBSharedTables& st, int E, int Epad, int P, int K, void* out, int32_t* kidx,
-                               hipStream_t s, int nimg = 1, int Bx = 0, int nbl = 16, bool raw = false);
+                               hipStream_t s, int nimg = 1, int Bx = 0, int nbl = 16, bool raw = false,
+                               const PassBYspec* ys = nullptr);
 hipError_t launch_passB_shared_phases(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* tw1, const SweepTables& tb,
                                       const PassBSharedTables& st, int E, int Epad, int P, int K, void* out, int32_t* kidx,
-                                      void* psi_out, hipStream_t s, int Bx, int nbl);
+                                      void* psi_out, hipStream_t s, int Bx, int nbl, const PassBYspec* ys = nullptr);
 // raw: the winners are left WITHOUT the candidate-independent compensation exp(2 pi i (ky + s_p / 16) y) (no second visit
 // of the rows: 0.8 GB less traffic at 4096^2 x 3); the consumer adds its phase step along y (launch_reconstruct_setup)
 

@@ -33,6 +33,7 @@
 
 #include "gpa_internal.h"
 #include "gpa_passb_shared.h"
+#include "gpa_yspec.h"
 
 namespace gpa {
 
@@ -169,14 +170,20 @@ struct PassBSGeom {
 // phase-gradient stencil of wfr2_grad_opt (geometric_phase_analysis.py:763-813).  The values in registers are the lock-ins
 // WITHOUT the candidate-independent phasor exp(2 pi i (ky + s / 16) y) -- compensation along x included --, so the stencil
 // subtracts that phasor's phase step per column and needs no 2 pi (w - k) (launch_phasegrad, compensated form).
-template <class T, int LG, bool PADDED, int EE, int NBL, bool PSI = false>
+// YSPEC: Tin holds FFT_y of the x-planes in the spectral register layout (pass A on spectrum columns), so a new
+// x-plane costs NBL loads instead of a row load and a forward transform: the band rotation by s blocks becomes the choice of
+// the stored blocks (yspec_source), the row scalar exp(-2 pi i (wx - kx) x) commutes with the transform, and the end strips --
+// spatial samples -- come from strips_in [image][plane][x][2 Epad] (passA_strips_kernel).
+template <class T, int LG, bool PADDED, int EE, int NBL, bool PSI = false, bool YSPEC = false>
 __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
                              (sizeof(T) == 8 ? GPA_PBS_F64_WAVES : (LG >= 13 ? GPA_PBS_L13_WAVES : (PADDED ? GPA_PBS_PAD_WAVES : GPA_PBS_F32_WAVES)))) void passB_shared_kernel(
     const cpx<T>* __restrict__ Tin, int n0, int n1, const T* __restrict__ Gb, const cpx<T>* __restrict__ twtab,
     const int* __restrict__ planeof, const int* __restrict__ order, const int* __restrict__ desc, const cpx<T>* __restrict__ pre_g,
     const cpx<T>* __restrict__ psi, const T* __restrict__ gtab, const cpx<T>* __restrict__ dx,
     const cpx<T>* __restrict__ dyc, const cpx<T>* __restrict__ rot16, int K, int E, int Epad, cpx<T>* out,
-    int32_t* kidx, int P, int Bx, int raw, T* __restrict__ psi_out) {
+    int32_t* kidx, int P, int Bx, int raw, T* __restrict__ psi_out, const cpx<T>* __restrict__ strips_in,
+    const int* __restrict__ shifts) {
+  static_assert(!YSPEC || (!PADDED && EE == 16 && NBL < EE), "y-spectral pass B: periodic rows, a rotated band");
   using F = WgFFT<T, LG, EE>;
   using G = PassBSGeom<T, LG, EE>;
   using V4 = typename MfmaVec<T>::type;
@@ -236,14 +243,47 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
   //  no longer wait for sixteen acknowledgements; the 16 registers it frees take the kernel from 68 to 12 bytes of
   //  scratch: pass B 3.06 -> 2.89 ms.  f32 measured the same either way and keeps it.)
   constexpr bool PREFETCH = NBL < EE && sizeof(T) == 4;
+  // YSPEC: the thread and the register offset of the stored spectrum that the band rotation of this peak selects
+  int ytq = tid, ysh = 0;
+  if constexpr (YSPEC) {
+    const YspecSrc y0s = yspec_source(LG, shifts[pt], tid, 0);
+    ytq = y0s.tid;
+    ysh = y0s.reg;
+  }
+  // end strips in the forms the matrix pass reads (it forms ONE real of t * p or t * conj(p) per lane as
+  // u p.x + v p.y): end 0 = T(j), j < E (feeds the outputs at the row's end), end 1 = T(n - 1 - j)
+  auto put_strips = [&](cpx<T> s0, cpx<T> s1) {
+    if constexpr (G::SV == 4) {
+      strip[0 * ES + tid] = {s0.x, -s0.y};   // end 0, real part of t p
+      strip[1 * ES + tid] = {s0.y, s0.x};    // end 0, imaginary part
+      strip[2 * ES + tid] = {s1.x, s1.y};    // end 1, real part of t conj(p)
+      strip[3 * ES + tid] = {s1.y, -s1.x};   // end 1, imaginary part
+    } else {
+      strip[0 * ES + tid] = {s0.x, s0.y};
+      strip[1 * ES + tid] = {s1.x, s1.y};
+    }
+  };
   for (int k = 0; k < K; ++k) {
     const int b = pt * K + k;      // position in visiting order: the candidate tables of this file
     const int ob = order[b];       // its position in the staged list: x-plane, compensation along x, reported index
     const int d = desc[b];
     if (d & 1) {
       // ---- a new x-plane: read its row once, take the end strips, forward transform -------------------------
-      const cpx<T>* src = Tin + (((size_t)img * Bx + planeof[ob]) * n0 + rr) * n1;
+      const size_t prow = ((size_t)img * Bx + planeof[ob]) * n0 + rr;
+      const cpx<T>* src = Tin + prow * n1;
       const cpx<T> cs0 = dx[(size_t)ob * n0 + rr];   // exp(-2 pi i (wx - kx) x): the same for every candidate of the plane
+      if constexpr (YSPEC) {
+        // the spectrum is there already: the live blocks of the rotated band, times the row scalar
+#pragma unroll
+        for (int i = 0; i < NBL; ++i) X[i] = cmul(load_once(src + ((i + ysh) & (EE - 1)) * TPF + ytq), cs0);
+        if (tid < Epad) {
+          const cpx<T>* sp = strips_in + prow * (2 * Epad);
+          const bool in = tid < E;
+          const cpx<T> s0 = in ? cmul(sp[tid], cmul(cs0, rot)) : cpx<T>{T(0), T(0)};
+          const cpx<T> s1 = in ? cmul(sp[2 * Epad - 1 - tid], cmul(cs0, rot_tail)) : cpx<T>{T(0), T(0)};
+          put_strips(s0, s1);
+        }
+      } else {
       const cpx<T> cs = cmul(cs0, rot);              // ... times the band rotation at this thread's columns
       cpx<T> tail = {T(0), T(0)};
       if (tid < E) tail = src[n1 - 1 - tid];
@@ -261,25 +301,16 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
         for (int i = 0; i < EE; ++i) XX[i] = cmul(load_once(src + tid + TPF * i), cs);
       }
       if (tid < Epad) {
-        // strips in the two forms the matrix pass reads (it forms ONE real of t * p or t * conj(p) per lane as
-        // u p.x + v p.y): end 0 = T(j), j < E (feeds the outputs at the row's end), end 1 = T(n - 1 - j)
         const bool in = tid < E;
         const cpx<T> s0 = in ? XX[0] : cpx<T>{T(0), T(0)};
         const cpx<T> s1 = in ? cmul(tail, cmul(cs0, rot_tail)) : cpx<T>{T(0), T(0)};
-        if constexpr (G::SV == 4) {
-          strip[0 * ES + tid] = {s0.x, -s0.y};   // end 0, real part of t p
-          strip[1 * ES + tid] = {s0.y, s0.x};    // end 0, imaginary part
-          strip[2 * ES + tid] = {s1.x, s1.y};    // end 1, real part of t conj(p)
-          strip[3 * ES + tid] = {s1.y, -s1.x};   // end 1, imaginary part
-        } else {
-          strip[0 * ES + tid] = {s0.x, s0.y};
-          strip[1 * ES + tid] = {s1.x, s1.y};
-        }
+        put_strips(s0, s1);
       }
       F::forward(XX, lds, tid, tw);
       // only the band's blocks are kept (the transform's other outputs are dead code)
 #pragma unroll
       for (int i = 0; i < NBL; ++i) X[i] = XX[i];
+      }
     }
     // ---- candidate b: shifted Gaussian, inverse transform (the matrix pass of a new chunk rides between its barriers)
     const int par = (d >> 7) & 1;   // parity of the chunk: which copy of the staged post-factors this candidate reads
@@ -568,17 +599,19 @@ hipError_t launch_shared_tables(int dtype, const Axis& a1, const double* wys, co
   return hipErrorInvalidValue;
 }
 
-template <class T, int LG, bool PADDED, int EE, int NBL, bool PSI = false>
+template <class T, int LG, bool PADDED, int EE, int NBL, bool PSI = false, bool YSPEC = false>
 static hipError_t run_passB_shared(const Axis& a1, int n0, const void* Tbuf, const void* tw1, const SweepTables& tb,
                                    const PassBSharedTables& st, int E, int Epad, int P, int K, void* out, int32_t* kidx,
-                                   hipStream_t s, int nimg, int Bx, bool raw, void* psi_out = nullptr) {
+                                   hipStream_t s, int nimg, int Bx, bool raw, void* psi_out = nullptr,
+                                   const PassBYspec* ys = nullptr) {
+  if (YSPEC && (!ys || !ys->strips || !ys->shifts)) return hipErrorInvalidValue;
   using G = PassBSGeom<T, LG, EE>;
   size_t lds = G::lds_bytes(Epad);
   if (lds > 160 * 1024 || E > G::TPF || Epad > G::TPF) return hipErrorInvalidValue;
   // (experiment switch PBS_LDS_PAD=<bytes>: extra dynamic LDS per workgroup, i.e. fewer rows per CU, so that kernels of other
   //  streams -- the unwrap of the previous image, bench.py --inflight 2 -- can share the CUs with this one)
   if (opt_set(OPT_PBS_LDS_PAD)) lds = std::min<size_t>(160 * 1024, lds + (size_t)opt(OPT_PBS_LDS_PAD).num);
-  auto kern = passB_shared_kernel<T, LG, PADDED, EE, NBL, PSI>;
+  auto kern = passB_shared_kernel<T, LG, PADDED, EE, NBL, PSI, YSPEC>;
   // (the dynamic LDS size depends on Epad: raise the limit whenever a larger one comes along)
   static int lds_set[32] = {0};
   int dev = 0;
@@ -592,7 +625,8 @@ static hipError_t run_passB_shared(const Axis& a1, int n0, const void* Tbuf, con
   GPA_PROF(PSI ? "passB_shared_phases_kernel" : "passB_shared_kernel", s);
   kern<<<grid, G::THREADS, lds, s>>>((const cpx<T>*)Tbuf, n0, a1.n, (const T*)st.Gb, (const cpx<T>*)tw1, tb.planeof, st.order, st.desc,
                                      (const cpx<T>*)st.pre, (const cpx<T>*)st.psi, (const T*)st.gtab, (const cpx<T>*)tb.dx,
-                                     (const cpx<T>*)st.dyc, (const cpx<T>*)st.rot16, K, E, Epad, (cpx<T>*)out, kidx, P, Bx, raw ? 1 : 0, (T*)psi_out);
+                                     (const cpx<T>*)st.dyc, (const cpx<T>*)st.rot16, K, E, Epad, (cpx<T>*)out, kidx, P, Bx, raw ? 1 : 0, (T*)psi_out,
+                                     (const cpx<T>*)(YSPEC ? ys->strips : nullptr), YSPEC ? ys->shifts : nullptr);
   return hipGetLastError();
 }
 
@@ -615,6 +649,11 @@ bool passB_shared_supports(int dtype, const Axis& a1, int E) {
 }
 
 // the live-register counts that are built: the smallest one that holds `need` blocks
+// can the y-spectral form run these rows with nbl live registers (the instantiations built above)?
+bool passB_yspec_supports(int dtype, const Axis& a1, int nbl) {
+  return !a1.padded && a1.n == a1.L && yspec_lg_ok(a1.lg) && (nbl == 8 || (nbl == 6 && dtype == 0));
+}
+
 int passB_shared_nbl(int dtype, int need) {
   if (dtype == 0 && need <= 6) return 6;
   if (need <= 8) return 8;
@@ -625,8 +664,18 @@ int passB_shared_nbl(int dtype, int need) {
 // psi_out [P][K (list positions)][n0][n1] reals.  Instantiated for the row classes the pipeline uses (2048 / 4096 / f32 8192).
 hipError_t launch_passB_shared_phases(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* tw1, const SweepTables& tb,
                                       const PassBSharedTables& st, int E, int Epad, int P, int K, void* out, int32_t* kidx,
-                                      void* psi_out, hipStream_t s, int Bx, int nbl) {
+                                      void* psi_out, hipStream_t s, int Bx, int nbl, const PassBYspec* ys) {
   if (!psi_out || !kidx) return hipErrorInvalidValue;
+  if (ys) {
+    // the y-spectral form: periodic rows of 2048 / 4096 points with a rotated band
+    if (a1.padded) return hipErrorInvalidValue;
+#define CASE_Y(T, LG, NBL) \
+    if (a1.lg == LG && nbl == NBL && dtype == (sizeof(T) == 4 ? 0 : 1)) \
+      return run_passB_shared<T, LG, false, 16, NBL, true, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, 1, Bx, false, psi_out, ys);
+    CASE_Y(float, 11, 6) CASE_Y(float, 12, 6) CASE_Y(float, 11, 8) CASE_Y(float, 12, 8) CASE_Y(double, 11, 8) CASE_Y(double, 12, 8)
+#undef CASE_Y
+    return hipErrorInvalidValue;
+  }
 #define CALL_P(T, LG, NBL) \
   (a1.padded ? run_passB_shared<T, LG, true, 16, NBL, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, 1, Bx, false, psi_out) \
              : run_passB_shared<T, LG, false, 16, NBL, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, 1, Bx, false, psi_out))
@@ -644,7 +693,16 @@ hipError_t launch_passB_shared_phases(int dtype, const Axis& a1, int n0, const v
 
 hipError_t launch_passB_shared(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* tw1, const SweepTables& tb,
                                const PassBSharedTables& st, int E, int Epad, int P, int K, void* out, int32_t* kidx,
-                               hipStream_t s, int nimg, int Bx, int nbl, bool raw) {
+                               hipStream_t s, int nimg, int Bx, int nbl, bool raw, const PassBYspec* ys) {
+  if (ys) {
+    if (a1.padded) return hipErrorInvalidValue;
+#define CASE_Y(T, LG, NBL) \
+    if (a1.lg == LG && nbl == NBL && dtype == (sizeof(T) == 4 ? 0 : 1)) \
+      return run_passB_shared<T, LG, false, 16, NBL, false, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, raw, nullptr, ys);
+    CASE_Y(float, 11, 6) CASE_Y(float, 12, 6) CASE_Y(float, 11, 8) CASE_Y(float, 12, 8) CASE_Y(double, 11, 8) CASE_Y(double, 12, 8)
+#undef CASE_Y
+    return hipErrorInvalidValue;
+  }
 #define CALL_S(T, LG, NBL) \
   (a1.padded ? run_passB_shared<T, LG, true, 16, NBL>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, raw) \
              : run_passB_shared<T, LG, false, 16, NBL>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, raw))

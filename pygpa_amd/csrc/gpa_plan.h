@@ -19,6 +19,7 @@
 #include "../../include/gpa_hip.h"
 #include "gpa_internal.h"
 #include "gpa_passb_shared.h"
+#include "gpa_yspec.h"
 #include "gpa_unwrap.h"
 #include "gpa_dft.h"
 #include "gpa_gaussfft.h"
@@ -134,6 +135,12 @@ struct gpa_plan {
   bool sh_built_ok = false;       // the tables of that key are complete and worth using
   bool sh_use = false;            // ... and the staged candidates form runs of >= 2 on an x-plane
   size_t sh_gb_bytes = 0, sh_psi_bytes = 0;
+  // y-spectral sweep: pass A filters columns of FFT_y(image), pass B runs no forward transform
+  bool ys_ok = false;             // the staged list / rows can take it (built with the shared tables)
+  bool ys_use = false;            // ... and the sweep being staged does (sweep_choose_path; NO_YSPEC=1 keeps the spatial path)
+  PassAYspec ys{};                // Yhat / strips (grown on demand, ensure_yspec), the (plane, block) pairs of the staged list
+  int* d_ys_pairs = nullptr;      // [16 max_batch]
+  size_t ys_yhat_bytes = 0, ys_strips_bytes = 0;
   std::vector<int> staged_planeof;
   void* Tbuf = nullptr;           // [tbuf_planes][n0][n1] complex: one plane per DISTINCT wx (x-plane), grown on demand
   int tbuf_planes = 0;
@@ -242,7 +249,13 @@ int stage_kmat(gpa_plan* p, const double* kvecs, int P);
 // the x-planes pass B reads: those of one image in the plan's own buffer ({p->Tbuf, 1, 0}), or those of a stack of nimg images
 // `stride` planes apart (stride != 0 marks a stack)
 struct XPlanes { const void* T; int nimg, stride; };
-int stage_sweep(gpa_plan* p, const double* krefs, int P, const double* klists, int K, double sigma, int* Bx);
+// passb: the pass B the caller will run on the staged planes -- SWEEP_PASSB_OTHER (per-candidate / gated / plain lock-ins:
+// spatial pass A), SWEEP_PASSB_SELECT (passB_select), SWEEP_PASSB_PHASES (passB_phases); the two shared-forward users decide
+// HERE, before pass A, whether the sweep takes the y-spectral path (p->ys_use)
+enum { SWEEP_PASSB_OTHER = 0, SWEEP_PASSB_SELECT = 1, SWEEP_PASSB_PHASES = 2 };
+int stage_sweep(gpa_plan* p, const double* krefs, int P, const double* klists, int K, double sigma, int* Bx,
+                int passb = SWEEP_PASSB_OTHER);
+int ensure_yspec(gpa_plan* p, int nimg, int Bx);
 int run_passA(gpa_plan* p, const void* image, const void* mean, void* Tbuf, int Bx, int nimg);
 int passB_select(gpa_plan* p, const XPlanes& xp, int P, int K, void* lockin, int32_t* kidx, bool raw);
 int passB_phases(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, void* psi, bool* shared);

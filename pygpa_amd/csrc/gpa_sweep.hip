@@ -14,6 +14,7 @@
 // first-maximum-wins rule, geometric_phase_analysis.py:679-684).
 #include "gpa_internal.h"
 #include "gpa_passb.h"
+#include "gpa_yspec.h"
 
 namespace gpa {
 
@@ -195,14 +196,21 @@ struct PassAGeom {
 // ---------------------------------------------------------------------------
 // pass A: x-axis filter on column tiles
 // ---------------------------------------------------------------------------
-template <class T, int LG, bool PADDED>
+// MODE: PA_SPATIAL = the image's columns, every plane, into Tbuf.  PA_YSPEC = the same filter on columns q of
+// Yhat = FFT_y(image - mean) (complex input, rowfft_kernel): the x filter commutes with the transform along y, so this leaves
+// FFT_y(T_plane) for pass B to read; one (plane, tile) per workgroup, only the tiles inside the blocks a plane's peaks read.
+// PA_STRIPS = the spatial filter on the column tiles that cover [0, E) and [n1 - E, n1) alone, into the compact strips
+// buffer [plane][x][opitch = 2 Epad]: the samples the end fix of pass B multiplies, which FFT_y(T) does not give.
+enum { PA_SPATIAL = 0, PA_YSPEC = 1, PA_STRIPS = 2 };
+template <class T, int LG, bool PADDED, int MODE = PA_SPATIAL>
 __global__ __launch_bounds__((PassAGeom<T, LG>::THREADS)) void passA_kernel(
     const T* __restrict__ image, const T* __restrict__ mean, int n0, int n1,
     const cpx<T>* __restrict__ cxb, const cpx<T>* __restrict__ sx, const cpx<T>* __restrict__ wxw,
     const cpx<T>* __restrict__ wxr, int extL, int extR,
     const typename HType<PADDED, T>::type* __restrict__ H,
     const cpx<T>* __restrict__ twtab, cpx<T>* __restrict__ Tout, int B, int bchunk, int stag_phases, int stag_ticks,
-    int stag_first, int rot_mul) {
+    int stag_first, int rot_mul, const cpx<T>* __restrict__ Yin, const int* __restrict__ pairs, int npairs, int ntl,
+    int opitch) {
   using F = WgFFT<T, LG>;
   using G = PassAGeom<T, LG>;
   constexpr int CT = G::CT, NT = G::NT, TPF = F::TPF, L = F::L;
@@ -216,35 +224,65 @@ __global__ __launch_bounds__((PassAGeom<T, LG>::THREADS)) void passA_kernel(
   // dispatch), so give each XCD a contiguous run of column tiles -- the tiles that
   // share a 128-byte line of the output then meet in one L2 and leave it as whole lines.
   int tile = xcd_tile(blockIdx.x, gridDim.x);
-  if (stag_phases < 0) {
+  if (MODE == PA_SPATIAL && stag_phases < 0) {
     // experiment (PA_STAG=-q): groups of q lines' worth of tiles dealt round-robin over the XCDs instead of one contiguous run
     // of tiles per XCD (the column strip an XCD writes then spans the whole row instead of 1 KB of it)
     constexpr int TPL0 = (128 / (int)(G::C * sizeof(cpx<T>))) > 0 ? (128 / (int)(G::C * sizeof(cpx<T>))) : 1;
     const int g = TPL0 * -stag_phases, x = blockIdx.x & 7, idx = blockIdx.x >> 3;
     if (gridDim.x % (8 * g) == 0) tile = ((idx / g) * 8 + x) * g + idx % g;
   }
-  const int y0 = tile * G::C + c * NT;
+  int y0 = tile * G::C + c * NT;   // first column of the thread (input)
+  int oy0 = y0;                    // ... and where it goes in a row of the output
+  int plane = 0;                   // PA_YSPEC: the one plane of this workgroup
+  const int op = MODE == PA_STRIPS ? opitch : n1;   // row pitch of the output
+  if constexpr (MODE == PA_YSPEC) {
+    // tile -> (line of TPL tiles inside a block, (plane, block) pair, tile of the line), the pair varying faster than the
+    // line: the workgroups in flight on an XCD complete whole 128-byte lines and spread their row pieces over the planes
+    constexpr int TPL = (128 / (int)(G::C * sizeof(cpx<T>))) > 0 ? (128 / (int)(G::C * sizeof(cpx<T>))) : 1;
+    const int tl = tile % TPL, pr = (tile / TPL) % npairs, ln = tile / (TPL * npairs);
+    const int pe = pairs[pr];      // plane | block << 16
+    plane = pe & 0xffff;
+    y0 = (pe >> 16) * (n1 >> 4) + (ln * TPL + tl) * G::C + c * NT;
+    oy0 = y0;
+  } else if constexpr (MODE == PA_STRIPS) {
+    // tiles 0 .. ntl-1 cover the first, ntl .. 2 ntl - 1 the last ntl C columns; the last ones land behind the first Epad
+    y0 = (tile < ntl ? tile * G::C : n1 - (2 * ntl - tile) * G::C) + c * NT;
+    oy0 = tile < ntl ? y0 : y0 - (n1 - opitch);
+  }
   // image stacks: blockIdx.z = image, its B planes behind those of the image before
-  image += (size_t)blockIdx.z * n0 * n1;
-  Tout += (size_t)blockIdx.z * B * n0 * n1;
-  const T m = mean ? mean[blockIdx.z] : T(0);
+  if constexpr (MODE == PA_YSPEC) Yin += (size_t)blockIdx.z * n0 * n1;
+  else image += (size_t)blockIdx.z * n0 * n1;
+  Tout += (size_t)blockIdx.z * B * n0 * op;
+  const T m = (MODE != PA_YSPEC && mean) ? mean[blockIdx.z] : T(0);
 
-  T val[NT][16];
+  T val[MODE == PA_YSPEC ? 1 : NT][16];
+  cpx<T> cval[MODE == PA_YSPEC ? NT : 1][16];
   unsigned wrapmask = 0, rightmask = 0;   // slots of the left / right periodic extension (padded mode)
 #pragma unroll
-  for (int n = 0; n < NT; ++n) {
-    const int y = y0 + n;
+  for (int i = 0; i < 16; ++i) {
+    const int slot = t + TPF * i;
+    const int xs = axis_src(slot, n0, L, PADDED, extL, extR);
+    if (PADDED && slot >= n0) { if (slot < n0 + extR) rightmask |= 1u << i; else wrapmask |= 1u << i; }
+    if constexpr (MODE == PA_YSPEC) {
+      // (n1 is a multiple of the tile and y0 of NT: the NT columns of the thread are one aligned load)
+      struct alignas(NT * sizeof(cpx<T>)) Cols { cpx<T> v[NT]; };
+      Cols cc;
 #pragma unroll
-    for (int i = 0; i < 16; ++i) {
-      const int slot = t + TPF * i;
-      const int xs = axis_src(slot, n0, L, PADDED, extL, extR);
-      val[n][i] = (y < n1 && xs >= 0) ? image[(size_t)xs * n1 + y] - m : T(0);
-      if (PADDED && slot >= n0) { if (slot < n0 + extR) rightmask |= 1u << i; else wrapmask |= 1u << i; }
+      for (int n = 0; n < NT; ++n) cc.v[n] = {T(0), T(0)};
+      if (xs >= 0) cc = *reinterpret_cast<const Cols*>(&Yin[(size_t)xs * n1 + y0]);
+#pragma unroll
+      for (int n = 0; n < NT; ++n) cval[n][i] = cc.v[n];
+    } else {
+#pragma unroll
+      for (int n = 0; n < NT; ++n) {
+        const int y = y0 + n;
+        val[n][i] = (y < n1 && xs >= 0) ? image[(size_t)xs * n1 + y] - m : T(0);
+      }
     }
   }
   typename F::KTw tw;
   F::load_twiddles(tw, twtab, t);
-  if (stag_phases > 1 && (int)blockIdx.x < stag_first) {
+  if (MODE == PA_SPATIAL && stag_phases > 1 && (int)blockIdx.x < stag_first) {
     // phase stagger (PA_STAG): the workgroups that assemble one 128-byte line of an x-plane stay in step, but the lines'
     // owners start their plane loops 1/phases of a plane period apart, so that the drain of one group of CUs meets the
     // transforms of another instead of the whole chip storing -- and then computing -- at once.  Only the first wave of
@@ -259,8 +297,8 @@ __global__ __launch_bounds__((PassAGeom<T, LG>::THREADS)) void passA_kernel(
     __syncthreads();
   }
 
-  const int b0 = blockIdx.y * bchunk;
-  const int b1 = (b0 + bchunk < B) ? b0 + bchunk : B;
+  const int b0 = MODE == PA_YSPEC ? plane : blockIdx.y * bchunk;
+  const int b1 = MODE == PA_YSPEC ? plane + 1 : ((b0 + bchunk < B) ? b0 + bchunk : B);
   // plane rotation (PA_ROT=<m>, default 1 for transforms of 4096 points and more, 0 = off): the owners of line q start their
   // plane loop at plane (q m) mod nb.  The workgroups of this kernel run in step (one per CU, same work), so without it the whole
   // chip stores 32-byte row pieces of ONE plane at a time, 32 KB apart; spread over the planes (128 MB apart) the same stores
@@ -278,7 +316,10 @@ __global__ __launch_bounds__((PassAGeom<T, LG>::THREADS)) void passA_kernel(
       if (PADDED && ((wrapmask >> i) & 1)) ph = cmul(ph, wxw[b]);
       if (PADDED && ((rightmask >> i) & 1)) ph = cmul(ph, wxr[b]);
 #pragma unroll
-      for (int n = 0; n < NT; ++n) x[n][i] = {val[n][i] * ph.x, val[n][i] * ph.y};
+      for (int n = 0; n < NT; ++n) {
+        if constexpr (MODE == PA_YSPEC) x[n][i] = cmul(cval[n][i], ph);
+        else x[n][i] = {val[n][i] * ph.x, val[n][i] * ph.y};
+      }
     }
     F::template forward_multi<NT, CT>(x, lds, LDS_NSTRIDE, t, tw);
     {
@@ -298,14 +339,14 @@ __global__ __launch_bounds__((PassAGeom<T, LG>::THREADS)) void passA_kernel(
     if constexpr (NT == 2) {
       // two adjacent columns of one row go out as a single 2-complex (16 B for f32) store
       // when the row pitch keeps that store naturally aligned
-      if (y0 + 1 < n1 && (n1 & 1) == 0) {
+      if (y0 + 1 < n1 && (op & 1) == 0) {
         paired = true;
         struct alignas(2 * sizeof(cpx<T>)) Pair { cpx<T> a, b; };
         auto put = [&](int i) {
           const int slot = t + TPF * i;
           if (!PADDED || slot < n0) {
             Pair pr = {x[0][i], x[1][i]};
-            *reinterpret_cast<Pair*>(&Tout[((size_t)b * n0 + slot) * n1 + y0]) = pr;
+            *reinterpret_cast<Pair*>(&Tout[((size_t)b * n0 + slot) * op + oy0]) = pr;
           }
         };
 #pragma unroll
@@ -320,7 +361,7 @@ __global__ __launch_bounds__((PassAGeom<T, LG>::THREADS)) void passA_kernel(
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             const int slot = t + TPF * i;
-            if (!PADDED || slot < n0) Tout[((size_t)b * n0 + slot) * n1 + y] = x[n][i];
+            if (!PADDED || slot < n0) Tout[((size_t)b * n0 + slot) * op + oy0 + n] = x[n][i];
           }
         }
       }
@@ -331,53 +372,124 @@ __global__ __launch_bounds__((PassAGeom<T, LG>::THREADS)) void passA_kernel(
 // ---------------------------------------------------------------------------
 // launchers
 // ---------------------------------------------------------------------------
-template <class T, int LG, bool PADDED>
+template <class T, int LG, bool PADDED, int MODE>
 static hipError_t run_passA(const Axis& a0, int n1, const void* image, const void* mean,
                             const SweepTables& tb, const void* Hx, const void* tw0, void* Tbuf,
-                            int B, hipStream_t s, int nimg) {
+                            int B, hipStream_t s, int nimg, const PassAYspec* ys) {
   using G = PassAGeom<T, LG>;
   if constexpr (!G::FITS) {
     return hipErrorInvalidValue;
   } else {
-    auto kern = passA_kernel<T, LG, PADDED>;
+    auto kern = passA_kernel<T, LG, PADDED, MODE>;
     static unsigned lds_set = 0;
     hipError_t e = set_dynamic_lds_once(reinterpret_cast<const void*>(kern), (int)G::LDS_BYTES, lds_set);
     if (e != hipSuccess) return e;
-    const int tiles = (n1 + G::C - 1) / G::C;
+    int tiles = (n1 + G::C - 1) / G::C, ntl = 0, opitch = n1;
+    if (MODE == PA_YSPEC) {
+      // (a block of n1 / 16 columns is whole 128-byte lines of whole tiles: the kernel's tile map relies on it)
+      if (n1 % (16 * G::C) || ((size_t)(n1 / 16) * sizeof(cpx<T>)) % 128 || ys->npairs < 1) return hipErrorInvalidValue;
+      tiles = ys->npairs * (n1 / 16 / G::C);
+    } else if (MODE == PA_STRIPS) {
+      ntl = (ys->E + G::C - 1) / G::C;
+      opitch = 2 * ys->Epad;
+      if (n1 % G::C || ntl * G::C > ys->Epad || 2 * ntl * G::C > n1) return hipErrorInvalidValue;
+      tiles = 2 * ntl;
+    }
     // split the lock-in loop over grid.y when there are too few column tiles to fill 256 CUs
     int ysplit = 1;
-    while (tiles * ysplit < 512 && ysplit < B) ysplit *= 2;
+    while (MODE != PA_YSPEC && tiles * ysplit < 512 && ysplit < B) ysplit *= 2;
     if (ysplit > B) ysplit = B;
     const int bchunk = (B + ysplit - 1) / ysplit;
     dim3 grid(tiles, (B + bchunk - 1) / bchunk, nimg);
     // PA_STAG=<phases> [PA_STAG_TICKS=<10-ns ticks per phase step>]: see the kernel
     const int stag = opt_set(OPT_PA_STAG) ? (int)opt(OPT_PA_STAG).num : 0;
     const int stag_ticks = opt_set(OPT_PA_STAG_TICKS) ? (int)opt(OPT_PA_STAG_TICKS).num : 800 / (stag > 1 ? stag : 1);
-    GPA_PROF("passA_kernel", s);
+    GPA_PROF(MODE == PA_STRIPS ? "passA_strips_kernel" : "passA_kernel", s);
     kern<<<grid, G::THREADS, G::LDS_BYTES, s>>>(
         (const T*)image, (const T*)mean, a0.n, n1, (const cpx<T>*)tb.cxb, (const cpx<T>*)tb.sx,
         (const cpx<T>*)tb.wxw, (const cpx<T>*)tb.wxr, a0.extL, a0.extR,
-        (const typename HType<PADDED, T>::type*)Hx, (const cpx<T>*)tw0, (cpx<T>*)Tbuf, B, bchunk, stag,
-        stag_ticks, device_cus(), opt_set(OPT_PA_ROT) ? (int)opt(OPT_PA_ROT).num : (LG >= 12 ? 1 : 0));
+        (const typename HType<PADDED, T>::type*)Hx, (const cpx<T>*)tw0, (cpx<T>*)(MODE == PA_STRIPS ? ys->strips : Tbuf), B, bchunk, stag,
+        stag_ticks, device_cus(), opt_set(OPT_PA_ROT) ? (int)opt(OPT_PA_ROT).num : (LG >= 12 ? 1 : 0),
+        (const cpx<T>*)(ys ? ys->Yhat : nullptr), ys ? ys->pairs : nullptr, ys ? ys->npairs : 0, ntl, opitch);
     return hipGetLastError();
   }
 }
 
+template <int MODE>
+static hipError_t dispatch_passA(int dtype, const Axis& a0, int n1, const void* image, const void* mean,
+                                 const SweepTables& tb, const void* Hx, const void* tw0, void* Tbuf,
+                                 int B, hipStream_t s, int nimg, const PassAYspec* ys) {
+#define CASE_A(LG)                                                                                \
+  case LG:                                                                                        \
+    if (dtype == 0)                                                                               \
+      return a0.padded ? run_passA<float, LG, true, MODE>(a0, n1, image, mean, tb, Hx, tw0, Tbuf, B, s, nimg, ys) \
+                       : run_passA<float, LG, false, MODE>(a0, n1, image, mean, tb, Hx, tw0, Tbuf, B, s, nimg, ys); \
+    else                                                                                          \
+      return a0.padded ? run_passA<double, LG, true, MODE>(a0, n1, image, mean, tb, Hx, tw0, Tbuf, B, s, nimg, ys) \
+                       : run_passA<double, LG, false, MODE>(a0, n1, image, mean, tb, Hx, tw0, Tbuf, B, s, nimg, ys);
+  switch (a0.lg) { GPA_FOR_LG(CASE_A) }
+#undef CASE_A
+  return hipErrorInvalidValue;
+}
 
 hipError_t launch_passA(int dtype, const Axis& a0, int n1, const void* image, const void* mean,
                         const SweepTables& tb, const void* Hx, const void* tw0, void* Tbuf,
                         int B, hipStream_t s, int nimg) {
-#define CASE_A(LG)                                                                                \
-  case LG:                                                                                        \
-    if (dtype == 0)                                                                               \
-      return a0.padded ? run_passA<float, LG, true>(a0, n1, image, mean, tb, Hx, tw0, Tbuf, B, s, nimg) \
-                       : run_passA<float, LG, false>(a0, n1, image, mean, tb, Hx, tw0, Tbuf, B, s, nimg); \
-    else                                                                                          \
-      return a0.padded ? run_passA<double, LG, true>(a0, n1, image, mean, tb, Hx, tw0, Tbuf, B, s, nimg) \
-                       : run_passA<double, LG, false>(a0, n1, image, mean, tb, Hx, tw0, Tbuf, B, s, nimg);
-  switch (a0.lg) { GPA_FOR_LG(CASE_A) }
-#undef CASE_A
-  return hipErrorInvalidValue;
+  return dispatch_passA<PA_SPATIAL>(dtype, a0, n1, image, mean, tb, Hx, tw0, Tbuf, B, s, nimg, nullptr);
+}
+
+// ---------------------------------------------------------------------------
+// y-spectral sweep: row pre-pass, pass A on spectrum columns, end strips
+// ---------------------------------------------------------------------------
+// One workgroup per image row: Yhat[row] = FFT_y(row - mean), register i of thread t stored at position i TPF + t (the
+// spectral register layout pass B works in); only the blocks some plane reads (blockmask) are written.
+template <class T, int LG>
+__global__ __launch_bounds__((WgFFT<T, LG, 16>::TPF)) void rowfft_kernel(const T* __restrict__ image, const T* __restrict__ mean,
+                                                                        int n0, const cpx<T>* __restrict__ twtab,
+                                                                        unsigned blockmask, cpx<T>* __restrict__ Yhat) {
+  using F = WgFFT<T, LG, 16>;
+  constexpr int TPF = F::TPF, L = F::L;
+  extern __shared__ __attribute__((aligned(16))) char smem[];
+  cpx<T>* lds = reinterpret_cast<cpx<T>*>(smem);
+  const int tid = threadIdx.x;
+  const size_t base = ((size_t)blockIdx.y * n0 + blockIdx.x) * L;   // (periodic rows: n1 == L)
+  const T m = mean ? mean[blockIdx.y] : T(0);
+  cpx<T> x[16];
+#pragma unroll
+  for (int i = 0; i < 16; ++i) x[i] = {image[base + tid + TPF * i] - m, T(0)};
+  typename F::Twiddles tw;
+  F::load_twiddles(tw, twtab, tid);
+  F::forward(x, lds, tid, tw);
+#pragma unroll
+  for (int i = 0; i < 16; ++i)
+    if ((blockmask >> i) & 1) Yhat[base + i * TPF + tid] = x[i];
+}
+
+template <class T, int LG>
+static hipError_t run_rowfft(int n0, const void* image, const void* mean, const void* tw1, const PassAYspec& ys, hipStream_t s,
+                             int nimg) {
+  using F = WgFFT<T, LG, 16>;
+  auto kern = rowfft_kernel<T, LG>;
+  static unsigned lds_set = 0;
+  constexpr int lds = (int)(F::LDS_ELEMS * sizeof(cpx<T>));
+  hipError_t e = set_dynamic_lds_once(reinterpret_cast<const void*>(kern), lds, lds_set);
+  if (e != hipSuccess) return e;
+  GPA_PROF("rowfft_kernel", s);
+  kern<<<dim3(n0, nimg), F::TPF, lds, s>>>((const T*)image, (const T*)mean, n0, (const cpx<T>*)tw1, ys.blockmask, (cpx<T>*)ys.Yhat);
+  return hipGetLastError();
+}
+
+hipError_t launch_passA_yspec(int dtype, const Axis& a0, const Axis& a1, const void* image, const void* mean,
+                              const SweepTables& tb, const void* Hx, const void* tw0, const void* tw1, void* Tbuf, int B,
+                              const PassAYspec& ys, hipStream_t s, int nimg) {
+  if (a1.padded || !yspec_lg_ok(a1.lg) || a1.n != a1.L) return hipErrorInvalidValue;
+  hipError_t e;
+  if (a1.lg == 11) e = dtype == 0 ? run_rowfft<float, 11>(a0.n, image, mean, tw1, ys, s, nimg) : run_rowfft<double, 11>(a0.n, image, mean, tw1, ys, s, nimg);
+  else e = dtype == 0 ? run_rowfft<float, 12>(a0.n, image, mean, tw1, ys, s, nimg) : run_rowfft<double, 12>(a0.n, image, mean, tw1, ys, s, nimg);
+  if (e != hipSuccess) return e;
+  e = dispatch_passA<PA_YSPEC>(dtype, a0, a1.n, nullptr, nullptr, tb, Hx, tw0, Tbuf, B, s, nimg, &ys);
+  if (e != hipSuccess) return e;
+  return dispatch_passA<PA_STRIPS>(dtype, a0, a1.n, image, mean, tb, Hx, tw0, Tbuf, B, s, nimg, &ys);
 }
 
 hipError_t launch_passB(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* Hy,
