@@ -314,7 +314,12 @@ int gpa_invert_u_overlap(gpa_plan* plan, const void* u, int iters, int edge, voi
 int gpa_invert_u(gpa_plan* plan, const void* u, int iters, int edge, void* out);
 /* both with scipy.ndimage's boundary mode as an argument (the `mode=` keyword of the two reference functions):
  * mode 0 = 'nearest' (their default, what the two entry points above run), 1 = 'constant' (cval 0; the last round of
- * invert_u_overlap passes cval = nan, geometric_phase_analysis.py:297-299).  overlap != 0: invert_u_overlap.      */
+ * invert_u_overlap passes cval = nan, geometric_phase_analysis.py:297-299), 2 = 'reflect' / 'grid-mirror', 3 = 'mirror',
+ * 4 = 'grid-wrap' (coordinate and taps folded by the mode's extension; cval is never used: no NaN).  Any other code is
+ * GPA_ERR_ARG.  'reflect' is the exact half-sample symmetric spline; SciPy's own 'reflect' prefilter differs from it on
+ * axes shorter than 12 samples (3.7e-6 of the field at n = 4, rounding from n = 12).  SciPy's 'wrap' (legacy: coordinates
+ * of period n - 1 over coefficients of period n) and 'grid-constant' (all NaN from the reference's cval = nan round) have
+ * no code.  overlap != 0: invert_u_overlap.                                                                       */
 int gpa_invert_u_mode(gpa_plan* plan, const void* u, int iters, int edge, int overlap, int mode, void* out);
 int gpa_undistort_image(gpa_plan* plan, const void* deformed, const void* u, void* out);
 /* The same on device pointers, enqueued on the plan's stream WITHOUT a host synchronisation (gpa_plan_sync, or

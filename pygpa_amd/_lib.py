@@ -164,6 +164,28 @@ def check(code, what):
         raise GPAError('%s failed (%d): %s' % (what, code, last_error()))
 
 
+# scipy.ndimage boundary modes of invert_u / invert_u_overlap -> the mode codes of gpa_invert_u_mode[_dev]
+_WARP_MODES = {'nearest': 0, 'constant': 1, 'reflect': 2, 'grid-mirror': 2, 'mirror': 3, 'grid-wrap': 4}
+_WARP_REFUSED = {
+    'wrap': "mode 'wrap' is scipy.ndimage's legacy mode (coordinates fold with period n - 1 over spline coefficients of "
+            "period n; SciPy's documentation points to 'grid-wrap'): use mode='grid-wrap'",
+    'grid-constant': "mode 'grid-constant' is not provided: with the cval = nan last round of invert_u_overlap SciPy pads "
+                     "with NaN before the spline prefilter, and the reference returns all NaN",
+}
+
+
+def warp_mode_code(mode):
+    """The library's code of a scipy.ndimage boundary mode of invert_u / invert_u_overlap: 0 'nearest', 1 'constant',
+    2 'reflect' and its synonym 'grid-mirror', 3 'mirror', 4 'grid-wrap'.  Every other mode raises NotImplementedError
+    (for 'wrap' and 'grid-constant' with the reason); needs no library."""
+    try:
+        return _WARP_MODES[mode]
+    except (KeyError, TypeError):
+        pass
+    raise NotImplementedError(_WARP_REFUSED.get(mode if isinstance(mode, str) else None,
+                                                'mode must be one of %s, not %r' % (', '.join(map(repr, _WARP_MODES)), mode)))
+
+
 _OPTION_VALUES = {}     # what this process has set through set_option (name -> str); a name that is absent follows the
 #                         library's start-up value, i.e. the GPA_<NAME> environment variable read once
 
@@ -345,16 +367,15 @@ class Plan:
                                                _ptr(dudx), _ptr(dudy), _ptr(wnorm)), 'gpa_reconstruct_prediff')
         return dudx, dudy, wnorm
 
-    _WARP_MODES = {'nearest': 0, 'constant': 1}
-
     def invert_u(self, us, iters=35, edge=0, mode='nearest'):
+        """invert_u of the reference on the plan's grid; mode: 'nearest', 'constant', 'reflect' / 'grid-mirror', 'mirror' or
+        'grid-wrap' (warp_mode_code)"""
         us = np.ascontiguousarray(us, dtype=self.rdtype)
         if us.shape != (2,) + self.shape:
             raise ValueError('us must have shape (2,) + plan shape')
-        if mode not in self._WARP_MODES:
-            raise NotImplementedError("mode must be 'nearest' or 'constant'")
+        code = warp_mode_code(mode)
         out = np.empty((2,) + self.shape, dtype=self.rdtype)
-        check(self.lib.gpa_invert_u_mode(self.handle, _ptr(us), int(iters), int(edge), 0, self._WARP_MODES[mode], _ptr(out)),
+        check(self.lib.gpa_invert_u_mode(self.handle, _ptr(us), int(iters), int(edge), 0, code, _ptr(out)),
               'gpa_invert_u_mode')
         return out
 
@@ -381,13 +402,14 @@ class Plan:
         return out
 
     def invert_u_overlap(self, us, iters=35, edge=0, mode='nearest'):
+        """invert_u_overlap of the reference, (2, n0 + 2 edge, n1 + 2 edge); mode as in invert_u.  Only 'constant' ends on a
+        cval = nan round: the folded modes 'reflect' / 'mirror' / 'grid-wrap' give every coordinate a value"""
         us = np.ascontiguousarray(us, dtype=self.rdtype)
         if us.shape != (2,) + self.shape:
             raise ValueError('us must have shape (2,) + plan shape')
-        if mode not in self._WARP_MODES:
-            raise NotImplementedError("mode must be 'nearest' or 'constant'")
+        code = warp_mode_code(mode)
         out = np.empty((2, self.shape[0] + 2 * edge, self.shape[1] + 2 * edge), dtype=self.rdtype)
-        check(self.lib.gpa_invert_u_mode(self.handle, _ptr(us), int(iters), int(edge), 1, self._WARP_MODES[mode], _ptr(out)),
+        check(self.lib.gpa_invert_u_mode(self.handle, _ptr(us), int(iters), int(edge), 1, code, _ptr(out)),
               'gpa_invert_u_mode')
         return out
 
@@ -482,10 +504,12 @@ class Plan:
 
     def invert_u_dev(self, u_ptr, out_ptr, scale=1.0, iters=35, edge=0, overlap=True, mode='nearest', rects=None):
         """invert_u_overlap / invert_u of scale * u on device pointers, enqueued on the plan's stream (no host sync);
-        rects = (r0, c0, h, w) or a list of such windows: only those parts of the output grid are computed"""
+        rects = (r0, c0, h, w) or a list of such windows: only those parts of the output grid are computed.  mode: as in
+        invert_u (an unknown one raises NotImplementedError)"""
+        code = warp_mode_code(mode)
         arr, n = self._rects(rects)
         check(self.lib.gpa_invert_u_mode_dev(self.handle, _ptr(int(u_ptr)), float(scale), int(iters), int(edge), int(bool(overlap)),
-                                             self._WARP_MODES[mode], arr, n, _ptr(int(out_ptr))), 'gpa_invert_u_mode_dev')
+                                             code, arr, n, _ptr(int(out_ptr))), 'gpa_invert_u_mode_dev')
 
     def undistort_image_dev(self, deformed_ptr, u_ptr, out_ptr, uinv_ptr=None, rects=None, scale=1.0):
         """undistort_image(deformed, scale * u) on device pointers, enqueued on the plan's stream (no host sync); uinv_ptr

@@ -24,7 +24,8 @@ static int check_rects(const int* rects, int nrect, int o0, int o1, const char* 
 static int check_invert_args(gpa_plan* p, const void* u, void* out, int iters, int edge, int mode) {
   if (!p || !u || !out) return fail(GPA_ERR_ARG, "gpa_invert_u: null argument");
   if (iters < 1 || edge < 0) return fail(GPA_ERR_ARG, "gpa_invert_u: need iters >= 1, edge >= 0");
-  if (mode != 0 && mode != 1) return fail(GPA_ERR_ARG, "gpa_invert_u_mode: mode must be 0 (nearest) or 1 (constant)");
+  if (mode < 0 || mode > 4)
+    return fail(GPA_ERR_ARG, "gpa_invert_u_mode: mode must be 0 (nearest), 1 (constant), 2 (reflect / grid-mirror), 3 (mirror) or 4 (grid-wrap)");
   return GPA_OK;
 }
 
@@ -155,8 +156,8 @@ int gpa_invert_u(gpa_plan* p, const void* u, int iters, int edge, void* out) {
   return invert_u_host(p, u, iters, edge, 0, 0, out);
 }
 
-// the two with scipy's boundary mode as an argument: 0 = 'nearest', 1 = 'constant' (the `mode=` keyword of
-// geometric_phase_analysis.py:248, :262); overlap != 0 = invert_u_overlap
+// the two with scipy's boundary mode as an argument: 0 = 'nearest', 1 = 'constant', 2 = 'reflect' / 'grid-mirror', 3 = 'mirror',
+// 4 = 'grid-wrap' (the `mode=` keyword of geometric_phase_analysis.py:248, :262); overlap != 0 = invert_u_overlap
 int gpa_invert_u_mode(gpa_plan* p, const void* u, int iters, int edge, int overlap, int mode, void* out) {
   return invert_u_host(p, u, iters, edge, overlap ? 1 : 0, mode, out);
 }

@@ -11,6 +11,15 @@
 //                  the 4 tap indices clamped to the padded array.
 //   mode constant: no padding, WHOLE-sample symmetric (mirror) extension for filter and taps,
 //                  cval where the coordinate leaves [0, n-1].
+//   modes reflect (= grid-mirror), mirror, grid-wrap: no padding either; the extension of the mode -- half-sample
+//                  symmetric, whole-sample symmetric, periodic with period n -- for the filter, for the coordinate
+//                  (folded into one period before floor(), gpa_spline.h: fold_coord) and for the taps; cval is never
+//                  used, so the last round of invert_u_overlap yields no NaN.  'reflect' is the EXACT half-sample
+//                  symmetric spline: SciPy's own 'reflect' prefilter truncates its initialisation and differs from it on
+//                  axes shorter than 12 samples (3.7e-6 of the field at n = 4, 4e-12 at n = 9, rounding from n = 12).
+//   Refused: 'wrap' (SciPy's legacy mode: coordinates fold with period n - 1 over coefficients of period n; its
+//                  documentation points to 'grid-wrap') and 'grid-constant' (with the cval = NaN last round of
+//                  invert_u_overlap SciPy pads with NaN BEFORE the prefilter: the reference returns all NaN).
 // The fixed-point inversion u_it(r) <- u(r + u_it(r)) is independent per pixel, so all its
 // rounds run inside one kernel launch.
 #include <math.h>
@@ -165,6 +174,42 @@ __global__ __launch_bounds__(256) void invert_constant_kernel(const T* __restric
       const int plain_left = (nan_last ? iters - 2 : iters - 1) - it;   // plain rounds the full count would still run
       if (!(plain_left & 1)) { v[0] = nv[0]; v[1] = nv[1]; }          // (odd: the cycle's other member, v itself)
       if (nan_last) interp_constant<T, 2, WIDE>(coef, n0, n1, xs + v[0], ys + v[1], (T)__builtin_nan(""), v);
+      break;
+    }
+    pv[0] = v[0];
+    pv[1] = v[1];
+    v[0] = nv[0];
+    v[1] = nv[1];
+  }
+  out[(size_t)i * o1 + j] = v[0];
+  out[(size_t)o0 * o1 + (size_t)i * o1 + j] = v[1];
+}
+
+// the same fixed point with scipy's modes 'reflect' / 'grid-mirror', 'mirror' and 'grid-wrap' (ext: the mode's extension):
+// coefficients of the unpadded field filtered with that extension, every round sampled through interp_folded -- no cval,
+// so the overlap variant has no round of its own.  The row-segment form of invert_constant_kernel: one pixel per lane,
+// all rounds in one launch, a wavefront leaves once every pixel is at a bitwise fixed point or in a cycle of two.
+template <class T, bool WIDE>
+__global__ __launch_bounds__(256) void invert_folded_kernel(const T* __restrict__ c0, const T* __restrict__ c1, int n0, int n1,
+                                                           int edge, int shift, int iters, int ext, T* __restrict__ out,
+                                                           int wr0, int wc0, int wc1, int all_rounds) {
+  const int o1 = n1 + 2 * edge, o0 = n0 + 2 * edge;
+  const int j = wc0 + blockIdx.x * 256 + threadIdx.x, i = wr0 + blockIdx.y;
+  if (j >= wc1) return;
+  const T* const coef[2] = {c0, c1};
+  const T xb = T(i - edge), yb = T(j - edge);
+  T v[2];
+  interp_folded<T, 2, WIDE>(coef, n0, n1, xb, yb, ext, v);
+  const T xs = xb - T(shift), ys = yb - T(shift);
+  T pv[2] = {(T)__builtin_nan(""), (T)__builtin_nan("")};   // the iterate before v
+  for (int it = 0; it < iters; ++it) {
+    T nv[2];
+    interp_folded<T, 2, WIDE>(coef, n0, n1, xs + v[0], ys + v[1], ext, nv);
+    // every pixel of the wavefront at a bitwise fixed point or in a cycle of two: the later rounds are known (see above)
+    const bool fixed = nv[0] == v[0] && nv[1] == v[1];
+    const bool cyc2 = nv[0] == pv[0] && nv[1] == pv[1];
+    if (!all_rounds && __all(fixed || cyc2)) {
+      if (!((iters - 1 - it) & 1)) { v[0] = nv[0]; v[1] = nv[1]; }
       break;
     }
     pv[0] = v[0];
@@ -517,6 +562,36 @@ hipError_t invert_constant_t(const T* d_u, int n0, int n1, T scale, int iters, i
   return e;
 }
 
+// modes 'reflect' / 'grid-mirror' (ext = EXT_REFLECT), 'mirror' (EXT_MIRROR), 'grid-wrap' (EXT_WRAP): the prefilter with the
+// mode's extension on the unpadded field, then the row-segment kernel on every window (shift: invert_u's; no NaN round)
+template <class T>
+hipError_t invert_folded_t(const T* d_u, int n0, int n1, T scale, int iters, int edge, int shift, int ext, T* d_out, hipStream_t s,
+                           WarpWs* ws, const int* rects, int nrect) {
+  const size_t npx = (size_t)n0 * n1;
+  hipError_t e = reserve(ws, 4 * npx * sizeof(T), s);   // scaled copy, tmp, coef0, coef1
+  if (e == hipSuccess) e = ensure_taps<T>(ws, s);
+  if (e != hipSuccess) return e;
+  T* buf = (T*)ws->buf;
+  const T* d_h = (const T*)ws->taps;
+  T *tmp = buf + npx, *c0 = buf + 2 * npx, *c1 = buf + 3 * npx;
+  for (int c = 0; c < 2 && e == hipSuccess; ++c)
+    e = prefilter<T>(d_u + (size_t)c * npx, n0, n1, ext, d_h, tmp, c == 0 ? c0 : c1, s, 0, scale);
+  if (e != hipSuccess) return e;
+  const int o1 = n1 + 2 * edge, o0 = n0 + 2 * edge;
+  const int allr = opt_set(OPT_LF_ALL_ROUNDS) ? 1 : 0;   // (diagnostic: every round of the fixed point, no early exit)
+  for (int q = 0; q < (nrect > 0 ? nrect : 1); ++q) {
+    const Win v = window(nrect > 0 ? rects + 4 * q : nullptr, o0, o1);
+    if (v.h <= 0 || v.w <= 0) continue;
+    GPA_PROF("invert_kernel", s);
+    const dim3 grid((v.w + 255) / 256, v.h);
+    if (npx * sizeof(T) < ((size_t)1 << 32))
+      invert_folded_kernel<T, false><<<grid, 256, 0, s>>>(c0, c1, n0, n1, edge, shift, iters, ext, d_out, v.r0, v.c0, v.c0 + v.w, allr);
+    else
+      invert_folded_kernel<T, true><<<grid, 256, 0, s>>>(c0, c1, n0, n1, edge, shift, iters, ext, d_out, v.r0, v.c0, v.c0 + v.w, allr);
+  }
+  return hipGetLastError();
+}
+
 // the fixed-point rounds of mode 'nearest' on the coefficients c0, c1 (m0 x m1 each) of nfr fields: field f reads its
 // coefficients cplane elements and writes its output oplane elements behind field f - 1's (nfr <= 65535: gridDim.z)
 template <class T>
@@ -705,6 +780,12 @@ void warp_ws_free(WarpWs* ws) {
 // host synchronisation (the workspace grows with one, the first time a shape needs more).
 hipError_t warp_invert_u(int dtype, const void* d_u, int n0, int n1, double scale, int iters, int edge, int shift,
                          void* d_out, hipStream_t s, int mode, int nan_last, WarpWs* ws, const int* rects, int nrect) {
+  if (mode >= 2) {
+    // 2 = 'reflect' / 'grid-mirror', 3 = 'mirror', 4 = 'grid-wrap' (checked by the entry points: gpa_api_warp.hip)
+    const int ext = mode == 2 ? EXT_REFLECT : (mode == 3 ? EXT_MIRROR : EXT_WRAP);
+    return dtype == 0 ? invert_folded_t<float>((const float*)d_u, n0, n1, (float)scale, iters, edge, shift, ext, (float*)d_out, s, ws, rects, nrect)
+                      : invert_folded_t<double>((const double*)d_u, n0, n1, scale, iters, edge, shift, ext, (double*)d_out, s, ws, rects, nrect);
+  }
   if (mode == 1)
     return dtype == 0 ? invert_constant_t<float>((const float*)d_u, n0, n1, (float)scale, iters, edge, shift, nan_last, (float*)d_out, s, ws, rects, nrect)
                       : invert_constant_t<double>((const double*)d_u, n0, n1, scale, iters, edge, shift, nan_last, (double*)d_out, s, ws, rects, nrect);

@@ -586,16 +586,24 @@ def gaussian_deconvolve(data, sigma, dr=20, balance=5000, dtype=None):
 def invert_u_overlap(us, iters=35, edge=0, mode='nearest', dtype=None):
     """Numerical inverse of the displacement `us` (geometric_phase_analysis.py:262-300):
     u_it(r + us(r)) = r, by `iters` rounds of cubic-spline resampling on the grid extended by
-    `edge` pixels.  mode: scipy.ndimage's 'nearest' (the reference's default) or 'constant' (cval 0, the last round
-    cval = nan as in the reference); the other scipy modes are not provided."""
+    `edge` pixels.  mode, as scipy.ndimage.map_coordinates takes it: 'nearest' (the reference's default); 'constant' (cval 0,
+    the last round cval = nan as in the reference); 'reflect' and its synonym 'grid-mirror' (half-sample symmetric),
+    'mirror' (whole-sample symmetric) and 'grid-wrap' (periodic with the frame's period) -- for a field that continues
+    symmetrically or periodically across the frame edge; these three ignore cval, so the result holds no NaN.  'reflect' is the
+    exact half-sample symmetric spline: SciPy's own 'reflect' prefilter is approximate on axes shorter than 12 samples (3.7e-6 of
+    the field at 4 samples, 4e-12 at 9) and agrees to rounding from 12 on.  Refused with NotImplementedError: 'wrap' (SciPy's
+    legacy mode, whose coordinates fold with period n - 1 over coefficients of period n: use 'grid-wrap') and 'grid-constant'
+    (with the cval = nan round SciPy pads with NaN before the prefilter: the reference returns all NaN)."""
+    _lib.warp_mode_code(mode)      # an unknown mode is refused before a plan (and the library) is touched
     us = np.asarray(us)
     plan = _lib.get_plan(us.shape[1:], 1, DEFAULT_DTYPE if dtype is None else dtype)
     return plan.invert_u_overlap(us, iters=iters, edge=edge, mode=mode)
 
 
 def invert_u(us, iters=35, edge=0, mode='nearest', dtype=None):
-    """The variant without overlap (geometric_phase_analysis.py:248-259): u_it on the image's own grid; mode 'nearest'
-    or 'constant' as above."""
+    """The variant without overlap (geometric_phase_analysis.py:248-259): u_it on the image's own grid; mode as above
+    (no round passes cval = nan here: 'constant' keeps 0 outside the frame)."""
+    _lib.warp_mode_code(mode)      # an unknown mode is refused before a plan (and the library) is touched
     us = np.asarray(us)
     plan = _lib.get_plan(us.shape[1:], 1, DEFAULT_DTYPE if dtype is None else dtype)
     return plan.invert_u(us, iters=iters, edge=edge, mode=mode)
