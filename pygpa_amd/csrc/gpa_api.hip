@@ -138,7 +138,7 @@ int plan_build(gpa_plan* p) {
   TRY(dmalloc(p, &p->d_wnorm, npx * p->rsz));
   TRY(dmalloc(p, &p->d_u, 2 * npx * p->rsz));
   TRY(dmalloc(p, (void**)&p->d_kmat, (size_t)p->max_peaks * 2 * sizeof(double)));
-  if (!p->spectral_only) {
+  if (!p->no_unwrap) {
     size_t before = 0;
     hipError_t e = unwrap_workspace_create(p->dtype, p->n0, p->n1, p->stream, &p->uw, &before);
     if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("unwrap workspace: ") + hipGetErrorString(e));
@@ -215,8 +215,11 @@ gpa_plan* gpa_plan_create(int device, int n0, int n1, int max_batch, int dtype) 
     delete p;
     return nullptr;
   }
-  // beyond an LDS-resident transform (f32: 16384 pow2 / 8192 other; f64: 8192 pow2 / 4096 other) the plan has no sweep / unwrap
+  // beyond an LDS-resident transform (f32: 16384 pow2 / 8192 other; f64: 8192 pow2 / 4096 other) the plan has no sweep ...
   p->spectral_only = p->ax0.lg > maxlg || p->ax1.lg > maxlg;
+  // ... and no unwrap, except that the f64 unwrap serves power-of-two axes of 16384 points as the f32 one does
+  auto unwrap_axis_ok = [&](const Axis& a) { return a.lg <= maxlg || (a.lg == 14 && a.n == 16384); };
+  p->no_unwrap = !(unwrap_axis_ok(p->ax0) && unwrap_axis_ok(p->ax1));
   if (plan_build(p) != GPA_OK) {
     std::string keep = g_err;
     gpa_plan_destroy(p);

@@ -36,12 +36,22 @@ static inline int fail(int code, const std::string& msg) { return gpa_fail(code,
       return fail(GPA_ERR_HIP, std::string(#expr) + ": " + hipGetErrorString(_e));            \
   } while (0)
 
+// the two limits are separate: the f64 unwrap reaches power-of-two axes of 16384 points, the f64 sweep stops at 8192
+#define NEED_SWEEP(p, what)                                                                                         \
+  do {                                                                                                             \
+    if ((p)->spectral_only)                                                                                        \
+      return fail(GPA_ERR_STATE, std::string(what) + ": this plan's image is too large for the sweep kernels "          \
+                                 "(an axis above 16384 pow2 / 8192 other in f32, 8192 / 4096 in f64); it serves per, "  \
+                                 "find_peaks, gaussian_deconvolve, the per-pixel entry points and, where the plan has " \
+                                 "one (f64: power-of-two axes up to 16384), the unwrap");                               \
+  } while (0)
+
 #define NEED_UNWRAP(p, what)                                                                                     \
   do {                                                                                                             \
     if (!(p)->uw.impl)                                                                                             \
       return fail(GPA_ERR_STATE, std::string(what) + ": this plan's image is too large for the sweep / unwrap kernels " \
-                                 "(an axis above 16384 pow2 / 8192 other in f32, 8192 / 4096 in f64); it serves per, "  \
-                                 "find_peaks, gaussian_deconvolve and the per-pixel entry points only");                 \
+                                 "(an axis above 16384 pow2 / 8192 other in f32, 16384 pow2 / 4096 other in f64); it "  \
+                                 "serves per, find_peaks, gaussian_deconvolve and the per-pixel entry points only");     \
   } while (0)
 
 #define TRY(expr)            \
@@ -99,10 +109,13 @@ struct EnqueueWorker {
 
 struct gpa_plan {
   int device = 0, dtype = 0, n0 = 0, n1 = 0, max_batch = 0;
-  // an axis beyond what one workgroup transforms (f32: 16384 pow2 / 8192 other; f64: 8192 pow2 / 4096 other): no sweep and no
-  // unwrap workspace -- the plan serves the plain-DFT rows (per, find_peaks, gaussian_deconvolve: any axis up to 65536) and
+  // an axis beyond what one workgroup transforms (f32: 16384 pow2 / 8192 other; f64: 8192 pow2 / 4096 other): no sweep
+  // -- the plan serves the plain-DFT rows (per, find_peaks, gaussian_deconvolve: any axis up to 65536) and
   // the per-pixel kernels (reconstruct, Lawler-Fujita, Jacobian / properties, plane fit)
   bool spectral_only = false;
+  // ... and no unwrap workspace either, unless the long axes are f64 power-of-two axes of 16384 points: the unwrap's
+  // half-length transforms and transform-free column solves reach those (gpa_unwrap_rowhalf.hip, gpa_unwrap_colhalf.hip)
+  bool no_unwrap = false;
   Axis ax0{}, ax1{};              // the geometry in use (depends on sigma for non-power-of-two axes)
   Axis ax0_full{}, ax1_full{};    // the plan's largest geometry (L >= 2n - 1): what the tables are sized for
   hipStream_t stream = nullptr;
@@ -280,7 +293,7 @@ int dmalloc(gpa_plan* p, void** ptr, size_t bytes);
 inline int unwrap_fail(hipError_t e) {
   if (e == hipErrorNotSupported)
     return fail(GPA_ERR_STATE, "unwrap: no kernels for this shape -- an image with an axis that is not a power of two needs both axes <= 8192 "
-                               "(f32) / 4096 (f64); powers of two go to 16384 / 8192 per axis (INTEGRATION.md, size limits)");
+                               "(f32) / 4096 (f64); powers of two go to 16384 per axis in both precisions (INTEGRATION.md, size limits)");
   return fail(GPA_ERR_HIP, std::string("unwrap: ") + hipGetErrorString(e));
 }
 int plan_build(gpa_plan* p);

@@ -569,6 +569,9 @@ hipError_t dispatch_colsolve(const Impl* w, int compat, hipStream_t s, const dou
   if (w->tritab && part_rho && want_tri && w->n0 / w->triR <= 1024)
     return w->dtype == 0 ? dispatch_colsolve_tri<float>(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin)
                          : dispatch_colsolve_tri<double>(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin);
+  // f64 columns of 16384 points: colsolve_kernel's packed-pair transform does not fit LDS (ColGeom::FITS) -- one column per
+  // half-length transform instead (gpa_unwrap_colhalf.hip)
+  if (colhalf_offered(w)) return colhalf_colsolve(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin);
 #define CASE(LG) case LG: return w->dtype == 0 ? run_colsolve<float, LG>(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin) \
                                                : run_colsolve<double, LG>(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin);
   switch (w->lg0) { GPA_FOR_LG(CASE) }

@@ -4,7 +4,8 @@
 //   gpa_unwrap_rows.hip     row kernels of the power-of-two fused iteration (rowdct_fused, rowidct_p, rowidct_pq);
 //   gpa_unwrap_rowhalf.hip  the same for rows of 8192 points and more (half-length transforms); gpa_unwrap_pqdct.hip the
 //                           stencil + forward transform in one launch; gpa_unwrap_rowpers.hip the persistent rowidct_p
-//   gpa_unwrap_cols.hip     column solves (DCT kernel, transform-free recursion, streamed recursion)
+//   gpa_unwrap_cols.hip     column solves (DCT kernel, transform-free recursion, streamed recursion); gpa_unwrap_colhalf.hip
+//                           the DCT kernel for f64 columns of 16384 points (half-length transforms)
 //   gpa_unwrap_stencil.hip  set-up, stencil (pq), phi flush, the scalar / elementwise kernels of the plain scheme
 //   gpa_unwrap_generic.hip  sizes that are not powers of two: mixed-radix fused kernels (gpa_unwrap_mr.h), Bluestein kernels
 //   gpa_unwrap_tables.hip   workspace creation: twiddles, eigenvalue tables, chirps, the recursion's per-column constants
@@ -53,6 +54,10 @@ struct Impl {
   void *wk0s;                // w_k along axis 0, spectral layout
   void *ha0[2], *ham0[2];    // 1 - cos term of axis-0 bins (spectral layout); [compat]
   void *hb1[2];              // 1 - cos term of axis-1 bins (natural); [compat]
+  // f64 columns of 16384 points beside a shorter row axis: one column per half-length transform (gpa_unwrap_colhalf.h)
+  void* tw0h;                // twiddles of length n0 / 2
+  void* wk0h;                // (w_k, E_k) along axis 0, k = 0 .. n0 / 2 - 1 in natural order
+  void *ha0h[2], *ham0h[2];  // 1 - cos term of axis-0 bins k and n0 - k (slot 0: bin n0 / 2), natural order; [compat]
   int col_mode;              // COLSOLVE of the current solve: 0 default, 1 tri, 2 fft, 3 stream (read once per solve)
   void* tritab;              // TriCol per column (square images): transform-free column solve
   int triQ, triS, triR;      // its launch geometry, fixed when the table is built (the table depends on it)
@@ -97,6 +102,7 @@ bool pow2_pqdct_offered(const Impl* w);
 hipError_t pow2_pqdct(const Impl* w, const void* p, const void* weight, double* part_pq, int* npq, hipStream_t s);
 // long rows: one row per half-length transform (gpa_unwrap_rowhalf.hip)
 bool rowhalf_offered(const Impl* w);
+bool rowhalf_only(const Impl* w);   // ... and no packed-pair kernel exists for these rows (f64, 16384 points)
 hipError_t rowhalf_rowdct(const Impl* w, const void* q, int ring, const double* part_pq, int npq, double* part_norm, int it,
                           int* nnorm, int init, hipStream_t s);
 hipError_t rowhalf_rowidct_p(const Impl* w, const void* pin, void* pout, const double* part_rho, int nrho, int it, hipStream_t s);
@@ -113,6 +119,10 @@ hipError_t pow2_rowidct_p_pers(const Impl* w, const void* pin, void* pout, const
 // columns (gpa_unwrap_cols.hip): every size
 hipError_t dispatch_colsolve(const Impl* w, int compat, hipStream_t s, const double* part_norm, int nnorm, int it,
                              double eps, double* part_rho, int* nrho, const void* zin);
+// columns too long for colsolve_kernel's packed-pair transform: one column per half-length transform (gpa_unwrap_colhalf.hip)
+bool colhalf_offered(const Impl* w);
+hipError_t colhalf_colsolve(const Impl* w, int compat, hipStream_t s, const double* part_norm, int nnorm, int it, double eps,
+                            double* part_rho, int* nrho, const void* zin);
 // streamed column solve (gpa_unwrap_colstream.hip)
 int colstream_chunk(int n0, int n1);   // rows per chunk it would use for this shape, 0 = not offered
 hipError_t build_streamtab(Impl* w, hipStream_t s, size_t* bytes);

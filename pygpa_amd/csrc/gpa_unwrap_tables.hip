@@ -1,6 +1,7 @@
 // a7, workspace of the weighted unwrap: buffers, twiddles, the Laplacian eigenvalue tables (phase_unwrap.py:106-115, with
 // the reference's swapped-axis quirk as table [1]), Bluestein chirps, mixed-radix plans, and the per-column constants of
 // the transform-free column solve.  Host code only.
+#include "gpa_unwrap_colhalf.h"
 #include "gpa_unwrap_impl.h"
 
 namespace gpa {
@@ -97,8 +98,11 @@ hipError_t unwrap_workspace_create(int dtype, int n0, int n1, hipStream_t s, Unw
   w->rsz = dtype == 0 ? 4 : 8;
   w->lg0 = ilog2_exact(n0);
   w->lg1 = ilog2_exact(n1);
+  // power-of-two axes go to 16384 points in both precisions (f64 at 16384: half-length transforms along the rows, the
+  // transform-free solves or the half-length kernel down the columns); the Bluestein / mixed-radix engines of the other
+  // sizes need a whole transform in LDS: 16384 points in f32, 8192 in f64
   const int maxlg = dtype == 0 ? 14 : 13;
-  const bool pow2ok = w->lg0 >= 6 && w->lg1 >= 6 && w->lg0 <= maxlg && w->lg1 <= maxlg;
+  const bool pow2ok = w->lg0 >= 6 && w->lg1 >= 6 && w->lg0 <= 14 && w->lg1 <= 14;
   auto blue_lg = [](int n) { int lg = 6; while ((1 << lg) < 2 * n - 1) ++lg; return lg; };
   w->lgb0 = blue_lg(n0);
   w->lgb1 = blue_lg(n1);
@@ -286,6 +290,23 @@ hipError_t unwrap_workspace_create(int dtype, int n0, int n1, hipStream_t s, Unw
       if ((e = upload(dtype, &w->ham0[compat], am, &bytes, s)) != hipSuccess) return e;
       if ((e = upload(dtype, &w->hb1[compat], b, &bytes, s)) != hipSuccess) return e;
     }
+    if (dtype == 1 && w->lg0 == 14) {
+      // f64 columns of 16384 points: the tables of the half-length column kernel, natural order (gpa_unwrap_colhalf.h)
+      const int h = n0 / 2;
+      std::vector<double> t((size_t)2 * h);
+      for (int k = 0; k < h; ++k) {
+        t[2 * k] = cos(-2.0 * M_PI * k / h);
+        t[2 * k + 1] = sin(-2.0 * M_PI * k / h);
+      }
+      if ((e = upload(dtype, &w->tw0h, t, &bytes, s)) != hipSuccess) return e;
+      for (int compat = 0; compat < 2; ++compat) {
+        std::vector<double> wsp, a, am;
+        colhalf_tables(n0, compat ? n1 : n0, wsp, a, am);
+        if (compat == 0 && (e = upload(dtype, &w->wk0h, wsp, &bytes, s)) != hipSuccess) return e;
+        if ((e = upload(dtype, &w->ha0h[compat], a, &bytes, s)) != hipSuccess) return e;
+        if ((e = upload(dtype, &w->ham0h[compat], am, &bytes, s)) != hipSuccess) return e;
+      }
+    }
     if (n0 == n1 && (e = build_tritab(w, s, &bytes)) != hipSuccess) return e;
     if (n0 == n1 && (e = build_streamtab(w, s, &bytes)) != hipSuccess) return e;
   }
@@ -306,7 +327,8 @@ void unwrap_workspace_destroy(UnwrapWorkspace* ws) {
   void* bufs[] = {w->r, w->p, w->p2, w->q, w->z, w->tw0, w->tw1, w->wk1, w->wk0s, w->ha0[0], w->ha0[1], w->ham0[0],
                   w->ham0[1], w->hb1[0], w->hb1[1], w->scal, w->flags, w->part, w->btw0, w->btw1, w->chirp0, w->chirp1,
                   w->bspec0, w->bspec1, w->gwk0, w->gwk1, w->gha0[0], w->gha0[1], w->gham0[0], w->gham0[1], w->tritab,
-                  w->mrW0, w->mrW1, w->mrB0, w->mrB1, w->strtab, w->strlam, w->stragg, w->strcar, w->tw1h};
+                  w->mrW0, w->mrW1, w->mrB0, w->mrB1, w->strtab, w->strlam, w->stragg, w->strcar, w->tw1h,
+                  w->tw0h, w->wk0h, w->ha0h[0], w->ha0h[1], w->ham0h[0], w->ham0h[1]};
   for (void* b : bufs)
     if (b) hipFree(b);
   for (int j = 2; j < w->nring; ++j)
