@@ -38,9 +38,25 @@ hipError_t run_pcg(Impl* w, const void* a, const void* b, const void* weight, bo
   // to reproduce, and the true Laplacian eigenvalues are used instead.
   if (compat && (n0 >= 2 * n1 || n1 >= 2 * n0)) compat = 0;
   {
-    const OptVal& mode = opt(OPT_COLSOLVE);   // once per solve: 0 default, 1 tri, 2 fft, 3 stream
-    w->col_mode = !mode.set ? 0 : (mode.str[0] == 't' ? 1 : (mode.str[0] == 's' ? 3 : 2));
-    w->lat_ok = !opt_set(OPT_NO_LAT);
+    // the kernels of this solve, chosen once: the workspace's shape and tables and the options as they stand now
+    // (gpa_unwrap_route.h has the rules)
+    RouteIn in;
+    in.dtype = w->dtype; in.n0 = n0; in.n1 = n1; in.lg0 = w->lg0; in.lg1 = w->lg1;
+    in.nprob = w->nprob; in.generic = w->generic; in.mr_ok = w->mr_ok;
+    in.has_rowhalf = w->tw1h != nullptr;
+    in.has_colhalf = w->wk0h != nullptr;
+    in.has_tri = w->tritab != nullptr; in.triR = w->triR;
+    in.has_stream = w->strtab != nullptr;
+    const OptVal& mode = opt(OPT_COLSOLVE);
+    in.col_mode = !mode.set ? 0 : (mode.str[0] == 't' ? 1 : (mode.str[0] == 's' ? 3 : 2));
+    in.no_lat = opt_set(OPT_NO_LAT);
+    in.no_rowhalf = opt_set(OPT_NO_ROWHALF);
+    in.rowhalf_minlg_set = opt_set(OPT_ROWHALF_MINLG);
+    if (in.rowhalf_minlg_set) in.rowhalf_minlg = (int)opt(OPT_ROWHALF_MINLG).num;
+    in.no_rowpers = opt_set(OPT_NO_ROWPERS);
+    in.no_rowpq = opt_set(OPT_NO_ROWPQ);
+    in.no_pqdct = opt_set(OPT_NO_PQDCT);
+    w->route = unwrap_route(in);
   }
   {
     // the f32 stagnation guard's count (pcg_breakdown (2)): 2 by default, F32_STALL=<n>, F32_STALL=0 = off
@@ -96,12 +112,8 @@ hipError_t run_pcg(Impl* w, const void* a, const void* b, const void* weight, bo
     if (w->nring < ring) ring = w->nring;   // out of memory: flush more often
     bool phi_unwritten = a == nullptr;   // prepared start: nobody has zeroed phi
     int nnorm = 0;
-    // one image with rows of at most 512 pixels: row kernel and stencil in one launch (rowidct_pq_kernel)
-    const bool rowpq = !w->generic && w->lat_ok && w->nprob <= 2 && w->lg1 <= GPA_ROWPQ_MAXLG && w->n0 >= 4 && !opt_set(OPT_NO_ROWPQ);
-    // rows of 2048 / 4096 points with the streamed column solve: stencil and row transform in one launch (pqdct_kernel),
-    // the residual update applied by the column solve's first launch -- five launches and 44 bytes per pixel per
-    // iteration instead of six and 48 (NO_PQDCT keeps the separate kernels)
-    const bool fuse_pq = !rowpq && pow2_pqdct_offered(w) && colstream_is_default(w) && !opt_set(OPT_NO_PQDCT);
+    // (rowpq: rowidct_p and the stencil in one launch; fuse_pq: the stencil and the next rowdct in one launch)
+    const bool rowpq = w->route.rowpq, fuse_pq = w->route.fuse_pq;
     for (int it = 0; it < kmax; ++it) {
       // (first iteration of a prepared start: the partial norms of r0 ride in the part_pq / npq arguments)
       const bool init = it == 0 && a == nullptr;

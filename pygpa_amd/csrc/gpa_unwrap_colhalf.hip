@@ -123,10 +123,9 @@ hipError_t run_colsolve_half(const Impl* w, int compat, hipStream_t s, const dou
 }  // namespace
 
 // f64 columns of 16384 points: the one length whose packed-pair transform (colsolve_kernel) does not fit LDS
-bool colhalf_offered(const Impl* w) { return w->dtype == 1 && w->lg0 == 14 && !w->generic && w->wk0h != nullptr; }
 hipError_t colhalf_colsolve(const Impl* w, int compat, hipStream_t s, const double* part_norm, int nnorm, int it, double eps,
                             double* part_rho, int* nrho, const void* zin) {
-  if (!colhalf_offered(w)) return hipErrorInvalidValue;
+  if (w->dtype != 1 || w->lg0 != 14 || !w->wk0h) return hipErrorInvalidValue;
   return run_colsolve_half<double, 14>(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin);
 }
 

@@ -463,7 +463,7 @@ hipError_t run_colsolve(const Impl* w, int compat, hipStream_t s, const double* 
   if constexpr (!ColGeom<T, LG>::FITS) return hipErrorInvalidValue;
   else {
     if (!part_rho) return hipErrorInvalidValue;   // (the only caller is the fused iteration)
-    const bool lat = unwrap_latency_tuned(w, LG);
+    const bool lat = w->route.lat_cols;
     // (the latency-tuned instantiation has its own tile geometry: narrower column tiles for one 512^2 image)
     auto launch = [&](auto latc) -> hipError_t {
       constexpr bool LATC = decltype(latc)::value;
@@ -541,37 +541,20 @@ hipError_t dispatch_colsolve_tri(const Impl* w, int compat, hipStream_t s, const
 }
 }  // namespace
 
-bool colstream_is_default(const Impl* w) {
-  return w->strtab && (w->col_mode == 3 || (w->col_mode == 0 && w->n0 >= GPA_COLSTREAM_MIN));
-}
+// the column solve the route names (gpa_unwrap_route.h has the rules and the measurements behind them)
 hipError_t dispatch_colsolve(const Impl* w, int compat, hipStream_t s, const double* part_norm, int nnorm, int it,
                              double eps, double* part_rho, int* nrho, const void* zin) {
-  // Square images from 4096 points a side: the streamed recursion (gpa_unwrap_colstream.hip) -- three launches that
-  // read 1 KiB row pieces at the streaming rate instead of one that holds whole columns and is down to 32 / 16 / 8-byte
-  // pieces at 4096 / 8192 / 16384 points.  COLSOLVE=stream forces it wherever it is offered, =tri / =fft the resident kernels.
-  if (part_rho && colstream_is_default(w))
-    return dispatch_colstream(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin);
-  if (w->generic && part_rho) {
-    // smooth sizes: the transform-free solve where it applies (square images; it is 2-3x faster than two mixed-radix
-    // transforms per column pair), COLSOLVE=fft keeps the transforms
-    if (w->tritab && w->col_mode != 2)
+  if (!part_rho) return hipErrorInvalidValue;   // (the only caller is the fused iteration)
+  switch (w->route.cols) {
+    case ColSolve::stream: return dispatch_colstream(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin);
+    case ColSolve::tri:
+      if (!w->tritab) return hipErrorInvalidValue;
       return w->dtype == 0 ? dispatch_colsolve_tri<float>(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin)
                            : dispatch_colsolve_tri<double>(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin);
-    return mr_colsolve(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin);
+    case ColSolve::mr: return mr_colsolve(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin);
+    case ColSolve::colhalf: return colhalf_colsolve(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin);
+    case ColSolve::dct: break;
   }
-  // Square images can solve the columns without a transform (colsolve_tri_kernel).  Measured at 4096^2 on MI355X
-  // (profiles/r02_colsolve_tri.txt): f64 1.54 ms per step against 2.0 for the DCT kernel (whose f64 transforms
-  // spill), f32 82 us per launch against 68 -- the f32 DCT kernel is the faster one.  So: f64 by default,
-  // COLSOLVE=tri / fft forces one or the other (tests compare the two).
-  // (f32 columns of 8192 points: the transform kernel is down to two column pairs -- 16-byte row segments -- per
-  //  workgroup there and loses to the recursion: 453 against ~330 us per launch)
-  const bool want_tri = w->col_mode ? w->col_mode == 1 : (w->dtype != 0 || w->lg0 >= 13);
-  if (w->tritab && part_rho && want_tri && w->n0 / w->triR <= 1024)
-    return w->dtype == 0 ? dispatch_colsolve_tri<float>(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin)
-                         : dispatch_colsolve_tri<double>(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin);
-  // f64 columns of 16384 points: colsolve_kernel's packed-pair transform does not fit LDS (ColGeom::FITS) -- one column per
-  // half-length transform instead (gpa_unwrap_colhalf.hip)
-  if (colhalf_offered(w)) return colhalf_colsolve(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin);
 #define CASE(LG) case LG: return w->dtype == 0 ? run_colsolve<float, LG>(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin) \
                                                : run_colsolve<double, LG>(w, compat, s, part_norm, nnorm, it, eps, part_rho, nrho, zin);
   switch (w->lg0) { GPA_FOR_LG(CASE) }

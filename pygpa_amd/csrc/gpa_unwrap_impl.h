@@ -9,6 +9,8 @@
 //   gpa_unwrap_stencil.hip  set-up, stencil (pq), phi flush, the scalar / elementwise kernels of the plain scheme
 //   gpa_unwrap_generic.hip  sizes that are not powers of two: mixed-radix fused kernels (gpa_unwrap_mr.h), Bluestein kernels
 //   gpa_unwrap_tables.hip   workspace creation: twiddles, eigenvalue tables, chirps, the recursion's per-column constants
+// Which of these kernels a solve runs is decided once per solve by unwrap_route() (gpa_unwrap_route.h, the one statement of
+// the rules and of their GPA_* thresholds) and kept in Impl::route; the dispatchers below switch on it.
 #pragma once
 #include <math.h>
 #include <stdlib.h>
@@ -21,6 +23,7 @@
 #include "gpa_mrfft.h"
 #include "gpa_internal.h"
 #include "gpa_unwrap.h"
+#include "gpa_unwrap_route.h"
 
 namespace gpa {
 
@@ -40,7 +43,7 @@ struct Impl {
   int nprob;                 // problems solved per launch (blockIdx.z): 1, or 2 x images of a batched driver call
   int cap;                   // problems the buffers hold (nprob <= cap: unwrap_set_active)
   int iters_slot;            // flags[iters_slot] = iterations performed (3: fused iteration, 0: plain scheme)
-  bool lat_ok;               // latency-tuned kernel variants allowed (GPA_NO_LAT unset), read once per solve
+  Route route;               // the kernels of the current solve (unwrap_route(), once per solve)
   bool supported;
   size_t rsz;
   void *r, *p, *p2, *q, *z;   // p / p2: double-buffered search direction (= ring[0], ring[1])
@@ -58,7 +61,6 @@ struct Impl {
   void* tw0h;                // twiddles of length n0 / 2
   void* wk0h;                // (w_k, E_k) along axis 0, k = 0 .. n0 / 2 - 1 in natural order
   void *ha0h[2], *ham0h[2];  // 1 - cos term of axis-0 bins k and n0 - k (slot 0: bin n0 / 2), natural order; [compat]
-  int col_mode;              // COLSOLVE of the current solve: 0 default, 1 tri, 2 fft, 3 stream (read once per solve)
   void* tritab;              // TriCol per column (square images): transform-free column solve
   int triQ, triS, triR;      // its launch geometry, fixed when the table is built (the table depends on it)
   // streamed column solve (gpa_unwrap_colstream.hip; square images): per-column constants, chunk sums, chunk carries
@@ -98,29 +100,23 @@ hipError_t pow2_rowidct_p(const Impl* w, const void* pin, void* pout, const doub
 hipError_t pow2_rowidct_pq(const Impl* w, const void* pin, void* pout, const void* weight, const double* part_rho,
                            int nrho, double* part_pq, int* npq_out, int it, hipStream_t s);
 // stencil + row transform in one launch (rows of 2048 / 4096 points): D = DCT_rows(A^T W^2 A p) into w->q, partial <p, q>
-bool pow2_pqdct_offered(const Impl* w);
 hipError_t pow2_pqdct(const Impl* w, const void* p, const void* weight, double* part_pq, int* npq, hipStream_t s);
 // long rows: one row per half-length transform (gpa_unwrap_rowhalf.hip)
-bool rowhalf_offered(const Impl* w);
-bool rowhalf_only(const Impl* w);   // ... and no packed-pair kernel exists for these rows (f64, 16384 points)
 hipError_t rowhalf_rowdct(const Impl* w, const void* q, int ring, const double* part_pq, int npq, double* part_norm, int it,
                           int* nnorm, int init, hipStream_t s);
 hipError_t rowhalf_rowidct_p(const Impl* w, const void* pin, void* pout, const double* part_rho, int nrho, int it, hipStream_t s);
 // persistent, software-pipelined rowidct_p for 4096-point f32 rows (gpa_unwrap_rowpers.hip; NO_ROWPERS: the one-pair-per-
 // workgroup kernel of gpa_unwrap_rows.hip)
 // gpa_unwrap_rowhalfpers.hip: the persistent, LDS-DMA-pipelined forms of the half-length kernels (f32, 8192 / 16384 points)
-bool rowhalfpers_offered(const Impl* w);
 hipError_t rowhalfpers_rowdct(const Impl* w, const void* q, int ring, const double* part_pq, int npq, double* part_norm, int it,
                               int* nnorm, int init, hipStream_t s);
 hipError_t rowhalfpers_rowidct_p(const Impl* w, const void* pin, void* pout, const double* part_rho, int nrho, int it, hipStream_t s);
-bool pow2_rowpers_offered(const Impl* w);
 hipError_t pow2_rowidct_p_pers(const Impl* w, const void* pin, void* pout, const double* part_rho, int nrho, int it,
                                hipStream_t s);
 // columns (gpa_unwrap_cols.hip): every size
 hipError_t dispatch_colsolve(const Impl* w, int compat, hipStream_t s, const double* part_norm, int nnorm, int it,
                              double eps, double* part_rho, int* nrho, const void* zin);
 // columns too long for colsolve_kernel's packed-pair transform: one column per half-length transform (gpa_unwrap_colhalf.hip)
-bool colhalf_offered(const Impl* w);
 hipError_t colhalf_colsolve(const Impl* w, int compat, hipStream_t s, const double* part_norm, int nnorm, int it, double eps,
                             double* part_rho, int* nrho, const void* zin);
 // streamed column solve (gpa_unwrap_colstream.hip)
@@ -132,7 +128,6 @@ hipError_t dispatch_colstream(const Impl* w, int compat, hipStream_t s, const do
 hipError_t dispatch_colstream_update(const Impl* w, int compat, hipStream_t s, int it, double eps, int ring, const void* dq,
                                      const double* part_pq, int npq, double* part_norm_out, int* nnorm_out, double* part_rho,
                                      int* nrho);
-bool colstream_is_default(const Impl* w);   // the streamed solve is what dispatch_colsolve would run for this workspace / mode
 // sizes that are not powers of two (gpa_unwrap_generic.hip)
 hipError_t mr_rowdct_fused(const Impl* w, const void* q, int ring, const double* part_pq, int npq, double* part_norm,
                            int it, int* nnorm, int init, hipStream_t s);
@@ -287,38 +282,12 @@ constexpr int unwrap_elems(int lg, size_t real_size) {
   return lg <= (real_size == 8 ? GPA_UNWRAP_E8_MAXLG_F64 : GPA_UNWRAP_E8_MAXLG) ? 8 : 16;
 }
 
-// One image per call and axes up to 1024: the fused kernels are bound by their chains of dependent memory round
-// trips, not by bandwidth or occupancy, and run as latency-tuned instantiations (every input requested before the
-// first wait: ~30 more registers).  Stacks of frames and larger images fill the GPU and keep the lean ones
-// (measured: 64 frames of 512^2 2596 -> 2475 Mpix/s and 2048^2 2565 -> 2493 with the latency-tuned kernels).
-// The two kinds evaluate the same formulas; the compiler contracts multiply-adds differently in places, so results
-// agree to rounding, not to the bit (GPA_NO_LAT=1 runs the lean kernels everywhere: tests use it to compare a stack
-// with single calls exactly).
-#ifndef GPA_UNWRAP_LAT_MAXLG
-#define GPA_UNWRAP_LAT_MAXLG 10
-#endif
-#ifndef GPA_ROWHALF_MINLG
-#define GPA_ROWHALF_MINLG 13   // rows from 2^13 points on: one row per half-length transform (gpa_unwrap_rows.hip)
-#endif
-#ifndef GPA_COLSTREAM_MIN
-#define GPA_COLSTREAM_MIN 2048   // square images from this side on take the streamed column solve by default (2048^2: 26 -> 19 us per iteration, 3000^2: 58 -> 43; 1024^2: slower)
-#endif
-#define GPA_ROWPQ_MAXLG 9   // rows up to 512 pixels: row kernel and stencil in one launch (rowidct_pq_kernel)
-inline bool unwrap_latency_tuned(const Impl* w, int lg) {
-  return w->lat_ok && w->nprob <= 2 && lg <= GPA_UNWRAP_LAT_MAXLG;
-}
-
-// rows per thread: the f32 tile of a thread (ROWS x 4 columns) has to leave room for the double-precision recursions
-// within the 128 VGPRs that 1024 threads per workgroup allow: 8 rows (32 registers); f64: 16 rows x 2 columns (64)
+// (the thresholds of the kernel choice -- GPA_UNWRAP_LAT_MAXLG, GPA_ROWHALF_MINLG, GPA_COLSTREAM_MIN, GPA_ROWPQ_MAXLG -- and
+//  the rows per thread of the transform-free column solve, tri_rows_for(): gpa_unwrap_route.h)
 template <class T> struct TriRows { static constexpr int value = sizeof(T) == 4 ? 8 : 16; };
-// Short columns take half as many rows per thread on twice the threads: with ~125 one-wavefront workgroups on 256
-// CUs the kernel is bound by the instruction stream of a wavefront (4089 instructions at 8 rows x 4 columns, a
-// quarter of them f64), not by anything the chip shares.  GPA_TRI_SMALL = largest n0 that does (diagnostic).
+// GPA_TRI_SMALL = largest n0 that takes half as many rows per thread (diagnostic)
 inline int tri_rows(size_t real_size, int n0) {
-  const int base = real_size == 4 ? 8 : 16;
-  if (real_size == 4 && n0 > 8192) return 2 * base;   // (1024 threads hold at most 1024 chunks)
-  const int small = opt_set(OPT_TRI_SMALL) ? (int)opt(OPT_TRI_SMALL).num : 640;
-  return n0 <= small ? base / 2 : base;
+  return opt_set(OPT_TRI_SMALL) ? tri_rows_for(real_size, n0, (int)opt(OPT_TRI_SMALL).num) : tri_rows_for(real_size, n0);
 }
 
 // threads side by side along a row (Q), chunks per workgroup (S, padded to whole wavefronts when there are several)

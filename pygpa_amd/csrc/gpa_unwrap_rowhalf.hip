@@ -300,6 +300,7 @@ hipError_t run_rowidct_p_half(const Impl* w, const void* pin, void* pout, const 
 // dispatch for gpa_unwrap_rows.hip: hipErrorInvalidValue where no half-length instantiation exists
 hipError_t rowhalf_rowdct(const Impl* w, const void* q, int ring, const double* part_pq, int npq, double* part_norm, int it,
                           int* nnorm, int init, hipStream_t s) {
+  if (!w->tw1h) return hipErrorInvalidValue;
   if (w->lg1 == 12) return w->dtype == 0 ? run_rowdct_half<float, 12>(w, q, ring, part_pq, npq, part_norm, it, nnorm, init, s)
                                           : run_rowdct_half<double, 12>(w, q, ring, part_pq, npq, part_norm, it, nnorm, init, s);
   if (w->lg1 == 13) return w->dtype == 0 ? run_rowdct_half<float, 13>(w, q, ring, part_pq, npq, part_norm, it, nnorm, init, s)
@@ -309,6 +310,7 @@ hipError_t rowhalf_rowdct(const Impl* w, const void* q, int ring, const double* 
   return hipErrorInvalidValue;
 }
 hipError_t rowhalf_rowidct_p(const Impl* w, const void* pin, void* pout, const double* part_rho, int nrho, int it, hipStream_t s) {
+  if (!w->tw1h) return hipErrorInvalidValue;
   if (w->lg1 == 12) return w->dtype == 0 ? run_rowidct_p_half<float, 12>(w, pin, pout, part_rho, nrho, it, s)
                                           : run_rowidct_p_half<double, 12>(w, pin, pout, part_rho, nrho, it, s);
   if (w->lg1 == 13) return w->dtype == 0 ? run_rowidct_p_half<float, 13>(w, pin, pout, part_rho, nrho, it, s)
@@ -317,9 +319,5 @@ hipError_t rowhalf_rowidct_p(const Impl* w, const void* pin, void* pout, const d
                                           : run_rowidct_p_half<double, 14>(w, pin, pout, part_rho, nrho, it, s);
   return hipErrorInvalidValue;
 }
-bool rowhalf_offered(const Impl* w) { return w->lg1 >= 12 && w->lg1 <= 14 && w->tw1h != nullptr; }
-// f64 rows of 16384 points have no packed-pair kernel to fall back to (its transform does not fit LDS): the half-length
-// kernels run whatever NO_ROWHALF / ROWHALF_MINLG say
-bool rowhalf_only(const Impl* w) { return w->dtype == 1 && w->lg1 == 14 && w->tw1h != nullptr; }
 
 }  // namespace gpa

@@ -430,16 +430,15 @@ hipError_t run_rowdct_halfpers(const Impl* w, const void* q, int ring, const dou
 
 }  // namespace
 
-bool rowhalfpers_offered(const Impl* w) {
-  return !w->generic && w->dtype == 0 && (w->lg1 == 13 || w->lg1 == 14) && w->tw1h != nullptr && w->n0 >= 64 && !opt_set(OPT_NO_ROWPERS);
-}
 hipError_t rowhalfpers_rowidct_p(const Impl* w, const void* pin, void* pout, const double* part_rho, int nrho, int it, hipStream_t s) {
+  if (w->dtype != 0 || !w->tw1h) return hipErrorInvalidValue;
   if (w->lg1 == 13) return run_rowidct_p_halfpers<13>(w, pin, pout, part_rho, nrho, it, s);
   if (w->lg1 == 14) return run_rowidct_p_halfpers<14>(w, pin, pout, part_rho, nrho, it, s);
   return hipErrorInvalidValue;
 }
 hipError_t rowhalfpers_rowdct(const Impl* w, const void* q, int ring, const double* part_pq, int npq, double* part_norm, int it,
                               int* nnorm, int init, hipStream_t s) {
+  if (w->dtype != 0 || !w->tw1h) return hipErrorInvalidValue;
   if (w->lg1 == 13) return run_rowdct_halfpers<13>(w, q, ring, part_pq, npq, part_norm, it, nnorm, init, s);
   if (w->lg1 == 14) return run_rowdct_halfpers<14>(w, q, ring, part_pq, npq, part_norm, it, nnorm, init, s);
   return hipErrorInvalidValue;

@@ -181,12 +181,9 @@ int pers_workgroups() {
 
 }  // namespace
 
-bool pow2_rowpers_offered(const Impl* w) {
-  return !w->generic && w->dtype == 0 && w->lg1 == 12 && (w->n0 % 2) == 0 && w->n0 >= 64 && !opt_set(OPT_NO_ROWPERS);
-}
-
 hipError_t pow2_rowidct_p_pers(const Impl* w, const void* pin, void* pout, const double* part_rho, int nrho, int it,
                                hipStream_t s) {
+  if (w->dtype != 0 || w->lg1 != 12) return hipErrorInvalidValue;
   using G = PersGeom<12>;
   auto kern = rowidct_p_pers_kernel<12>;
   static unsigned lds_set = 0;

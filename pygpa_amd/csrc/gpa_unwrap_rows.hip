@@ -433,7 +433,7 @@ hipError_t run_rowdct_fused(const Impl* w, const void* q, int ring, const double
                             double* part_norm, int it, int* nnorm, int init, hipStream_t s) {
   if constexpr (!RowGeom<T, LG>::FITS) return hipErrorInvalidValue;
   else {
-    const bool lat = unwrap_latency_tuned(w, LG);
+    const bool lat = w->route.lat_rows;
     auto launch = [&](auto latc) -> hipError_t {
       constexpr bool LATC = decltype(latc)::value;
       using G = RowGeom<T, LG, LATC>;
@@ -459,7 +459,7 @@ hipError_t run_rowidct_p(const Impl* w, const void* pin, void* pout, const doubl
                          hipStream_t s) {
   if constexpr (!RowGeom<T, LG>::FITS) return hipErrorInvalidValue;
   else {
-    const bool lat = unwrap_latency_tuned(w, LG);
+    const bool lat = w->route.lat_rows;
     auto launch = [&](auto latc) -> hipError_t {
       constexpr bool LATC = decltype(latc)::value;
       using G = RowGeom<T, LG, LATC>;
@@ -499,12 +499,6 @@ hipError_t run_rowidct_pq(const Impl* w, const void* pin, void* pout, const void
     return hipGetLastError();
   }
 }
-
-// rows of 8192 points and more take the half-length kernels (NO_ROWHALF: the packed ones, for tests and measurements)
-inline bool use_row_half(const Impl* w) {
-  const int minlg = opt_set(OPT_ROWHALF_MINLG) ? (int)opt(OPT_ROWHALF_MINLG).num : GPA_ROWHALF_MINLG;
-  return w->lg1 >= minlg && w->lg1 >= 12 && w->tw1h && !opt_set(OPT_NO_ROWHALF);
-}
 }  // namespace
 
 hipError_t pow2_rowidct_pq(const Impl* w, const void* pin, void* pout, const void* weight, const double* part_rho,
@@ -517,9 +511,13 @@ hipError_t pow2_rowidct_pq(const Impl* w, const void* pin, void* pout, const voi
 }
 hipError_t pow2_rowidct_p(const Impl* w, const void* pin, void* pout, const double* part_rho, int nrho, int it,
                           hipStream_t s) {
-  if ((use_row_half(w) || rowhalf_only(w)) && rowhalf_offered(w))
-    return rowhalfpers_offered(w) ? rowhalfpers_rowidct_p(w, pin, pout, part_rho, nrho, it, s) : rowhalf_rowidct_p(w, pin, pout, part_rho, nrho, it, s);
-  if (pow2_rowpers_offered(w)) return pow2_rowidct_p_pers(w, pin, pout, part_rho, nrho, it, s);
+  switch (w->route.inv) {
+    case RowInv::halfpers: return rowhalfpers_rowidct_p(w, pin, pout, part_rho, nrho, it, s);
+    case RowInv::half: return rowhalf_rowidct_p(w, pin, pout, part_rho, nrho, it, s);
+    case RowInv::pers: return pow2_rowidct_p_pers(w, pin, pout, part_rho, nrho, it, s);
+    case RowInv::packed: break;
+    case RowInv::mr: return hipErrorInvalidValue;   // (run_pcg sends generic sizes to mr_rowidct_p)
+  }
 #define CASE(LG) case LG: return w->dtype == 0 ? run_rowidct_p<float, LG>(w, pin, pout, part_rho, nrho, it, s) \
                                                : run_rowidct_p<double, LG>(w, pin, pout, part_rho, nrho, it, s);
   switch (w->lg1) { GPA_FOR_LG(CASE) }
@@ -529,13 +527,12 @@ hipError_t pow2_rowidct_p(const Impl* w, const void* pin, void* pout, const doub
 // init: first iteration of a solve on prepared residuals -- part_pq / npq are then the producer's partial norms
 hipError_t pow2_rowdct_fused(const Impl* w, const void* q, int ring, const double* part_pq, int npq, double* part_norm,
                              int it, int* nnorm, int init, hipStream_t s) {
-  // f64 rows of 4096 points: the forward kernel alone gains from the half-length form (116 -> 99 us per launch; the inverse
-  // loses, 95 -> 126, and stays packed)
-  if (w->dtype == 1 && w->lg1 == 12 && w->tw1h && !opt_set(OPT_NO_ROWHALF) && !opt_set(OPT_ROWHALF_MINLG))
-    return rowhalf_rowdct(w, q, ring, part_pq, npq, part_norm, it, nnorm, init, s);
-  if ((use_row_half(w) || rowhalf_only(w)) && rowhalf_offered(w))
-    return rowhalfpers_offered(w) ? rowhalfpers_rowdct(w, q, ring, part_pq, npq, part_norm, it, nnorm, init, s)
-                                  : rowhalf_rowdct(w, q, ring, part_pq, npq, part_norm, it, nnorm, init, s);
+  switch (w->route.fwd) {
+    case RowFwd::halfpers: return rowhalfpers_rowdct(w, q, ring, part_pq, npq, part_norm, it, nnorm, init, s);
+    case RowFwd::half: return rowhalf_rowdct(w, q, ring, part_pq, npq, part_norm, it, nnorm, init, s);
+    case RowFwd::packed: break;
+    case RowFwd::mr: return hipErrorInvalidValue;   // (run_pcg sends generic sizes to mr_rowdct_fused)
+  }
 #define CASE(LG) case LG: return w->dtype == 0 ? run_rowdct_fused<float, LG>(w, q, ring, part_pq, npq, part_norm, it, nnorm, init, s) \
                                                : run_rowdct_fused<double, LG>(w, q, ring, part_pq, npq, part_norm, it, nnorm, init, s);
   switch (w->lg1) { GPA_FOR_LG(CASE) }

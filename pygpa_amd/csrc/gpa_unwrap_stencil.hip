@@ -517,7 +517,7 @@ hipError_t pq_t(const Impl* w, const void* p, const void* weight, int it, double
   const size_t npx = (size_t)n0 * n1;
   const dim3 grid(g.g.x, g.g.y, w->nprob);
   GPA_PROF("pq_kernel", s);
-  if (g.band == 4 && w->lat_ok && w->nprob <= 2 && npx <= ((size_t)1 << 20)) {
+  if (g.band == 4 && w->route.lat_pq && npx <= ((size_t)1 << 20)) {
     if (g.V == 4) pq_small_kernel<T, 4, 4><<<grid, 256, 0, s>>>((const T*)p, (const T*)weight, n0, n1, (T*)w->q, part_pq, w->flags, npx);
     else pq_small_kernel<T, 1, 4><<<grid, 256, 0, s>>>((const T*)p, (const T*)weight, n0, n1, (T*)w->q, part_pq, w->flags, npx);
   } else if (g.V == 4) {

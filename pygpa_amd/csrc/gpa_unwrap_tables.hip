@@ -238,7 +238,7 @@ hipError_t unwrap_workspace_create(int dtype, int n0, int n1, hipStream_t s, Unw
       e = upload(dtype, ax == 0 ? &w->tw0 : &w->tw1, t, &bytes, s);
       if (e != hipSuccess) return e;
     }
-    if (w->lg1 >= 12) {   // (rows of 4096 points can be switched to the half-length kernels for measurements: ROWHALF_MINLG)
+    if (unwrap_builds_rowhalf(w->lg1)) {   // (rows of 4096 points can be switched to the half-length kernels for measurements: ROWHALF_MINLG)
       const int h = n1 / 2;
       std::vector<double> t((size_t)2 * h);
       for (int k = 0; k < h; ++k) {
@@ -290,7 +290,7 @@ hipError_t unwrap_workspace_create(int dtype, int n0, int n1, hipStream_t s, Unw
       if ((e = upload(dtype, &w->ham0[compat], am, &bytes, s)) != hipSuccess) return e;
       if ((e = upload(dtype, &w->hb1[compat], b, &bytes, s)) != hipSuccess) return e;
     }
-    if (dtype == 1 && w->lg0 == 14) {
+    if (unwrap_builds_colhalf(dtype, w->lg0)) {
       // f64 columns of 16384 points: the tables of the half-length column kernel, natural order (gpa_unwrap_colhalf.h)
       const int h = n0 / 2;
       std::vector<double> t((size_t)2 * h);
@@ -307,11 +307,10 @@ hipError_t unwrap_workspace_create(int dtype, int n0, int n1, hipStream_t s, Unw
         if ((e = upload(dtype, &w->ham0h[compat], am, &bytes, s)) != hipSuccess) return e;
       }
     }
-    if (n0 == n1 && (e = build_tritab(w, s, &bytes)) != hipSuccess) return e;
-    if (n0 == n1 && (e = build_streamtab(w, s, &bytes)) != hipSuccess) return e;
   }
-  if (w->supported && w->generic && w->mr_ok && n0 == n1 && (e = build_tritab(w, s, &bytes)) != hipSuccess) return e;
-  if (w->supported && w->generic && w->mr_ok && n0 == n1 && (n1 % 4) == 0 && (e = build_streamtab(w, s, &bytes)) != hipSuccess) return e;
+  // the per-column constants of the transform-free and of the streamed column solve: square images on the fused path
+  if (w->supported && unwrap_builds_tri(w->generic, w->mr_ok, n0, n1) && (e = build_tritab(w, s, &bytes)) != hipSuccess) return e;
+  if (w->supported && unwrap_builds_stream(w->generic, w->mr_ok, n0, n1) && (e = build_streamtab(w, s, &bytes)) != hipSuccess) return e;
   if (bytes_out) *bytes_out = bytes;
   return hipSuccess;
 }
