@@ -207,11 +207,15 @@ int shared_prepare(gpa_plan* p, int P, int K) {
   const int B = P * K;
   if (!p->sh_ok || !p->use_shared || K < 2 || (int)p->staged_planeof.size() < B) return GPA_OK;
   const bool reorder = !opt_set(OPT_NO_REORDER);
-  if (p->sh_built_epoch == p->sh_epoch && p->sh_built_K == K && p->sh_built_B == B && p->sh_built_reorder == reorder) {
+  // planes per workgroup of the y-spectral pass A (YSPEC_GROUP=<n>, 1 = one plane per workgroup)
+  const int gmax = opt_set(OPT_YSPEC_GROUP) ? std::max(1, (int)opt(OPT_YSPEC_GROUP).num) : yspec_group_default(p->dtype);
+  if (p->sh_built_epoch == p->sh_epoch && p->sh_built_K == K && p->sh_built_B == B && p->sh_built_reorder == reorder &&
+      p->ys_gmax == gmax) {
     p->sh_use = p->sh_built_ok;
     return GPA_OK;
   }
   p->sh_built_reorder = reorder;
+  p->ys_gmax = gmax;
   // (the cache key is committed only when the tables are complete: a failed allocation below must not leave a key
   //  that sends the next call to the kernel with freed tables -- ADVICE r03)
   p->sh_built_epoch = -1;
@@ -366,32 +370,31 @@ int shared_prepare(gpa_plan* p, int P, int K) {
   HIP_TRY(hipStreamSynchronize(p->stream));   // `desc`, `order` are locals
   // y-spectral sweep: which blocks of n1 / 16 stored positions of every x-plane's spectrum pass B will read -- the union, over the
   // peaks whose candidates use the plane, of the blocks their band rotation selects (yspec_blockmask) -- as a list of
-  // (plane, block) pairs for pass A.  The list is dealt by block slot, so that neighbouring entries are different planes.
+  // (plane, block) pairs for pass A, gathered by block into groups of at most gmax planes (yspec_groups): a workgroup loads its
+  // tile of the block once for all planes of its group.
   p->ys_ok = false;
   if (passB_yspec_supports(p->dtype, p->ax1s, p->sh_nbl) && p->ax1s.L == p->ax1.L && !p->ax1.padded) {
     const int nplanes = p->last_planes;
     std::vector<unsigned> mask((size_t)nplanes, 0u);
     for (int b = 0; b < B; ++b) mask[p->staged_planeof[b]] |= yspec_blockmask(p->ax1s.lg, shifts[b / K], p->sh_nbl);
-    std::vector<int> pairs;
     unsigned all = 0;
-    for (int slot = 0; slot < 16; ++slot)
-      for (int q = 0; q < nplanes; ++q) {
-        int seen = 0;
-        for (int blk = 0; blk < 16; ++blk)
-          if ((mask[q] >> blk) & 1) {
-            if (seen++ == slot) pairs.push_back(q | (blk << 16));
-          }
-        all |= mask[q];
-      }
-    if (!p->d_ys_pairs) TRY(dmalloc(p, (void**)&p->d_ys_pairs, (size_t)p->max_batch * 16 * sizeof(int)));
-    HIP_TRY(hipMemcpyAsync(p->d_ys_pairs, pairs.data(), pairs.size() * sizeof(int), hipMemcpyHostToDevice, p->stream));
-    HIP_TRY(hipStreamSynchronize(p->stream));   // `pairs` is a local
-    p->ys.pairs = p->d_ys_pairs;
-    p->ys.npairs = (int)pairs.size();
+    for (int q = 0; q < nplanes; ++q) all |= mask[q];
+    const YspecGroups yg = yspec_groups(mask.data(), nplanes, gmax);
+    const size_t cap = (size_t)p->max_batch * 16;   // entries: at most 16 blocks of at most max_batch planes
+    if (yg.planes.size() > cap) return GPA_ERR_STATE;
+    std::vector<int> stage(yg.planes);
+    stage.resize(cap, 0);
+    for (const YspecGroup& g : yg.groups) { stage.push_back(g.block); stage.push_back(g.first); stage.push_back(g.count); }
+    if (!p->d_ys_groups) TRY(dmalloc(p, (void**)&p->d_ys_groups, cap * 4 * sizeof(int)));
+    HIP_TRY(hipMemcpyAsync(p->d_ys_groups, stage.data(), stage.size() * sizeof(int), hipMemcpyHostToDevice, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));   // `stage` is a local
+    p->ys.planes = p->d_ys_groups;
+    p->ys.groups = p->d_ys_groups + cap;
+    p->ys.ngroups = (int)yg.groups.size();
     p->ys.blockmask = all;
     p->ys.E = p->sh_E;
     p->ys.Epad = p->sh_Epad;
-    p->ys_ok = !pairs.empty();
+    p->ys_ok = !yg.groups.empty();
   }
   p->sh_built_epoch = p->sh_epoch;
   p->sh_built_K = K;

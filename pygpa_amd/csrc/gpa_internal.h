@@ -93,7 +93,7 @@ enum OptKey {
   OPT_PBS_FULLBAND, OPT_SERIAL_UNWRAP, OPT_NO_WORKER, OPT_NO_KSPLIT, OPT_NO_COMPACT, OPT_NO_SHARED,
   OPT_NO_PAIR, OPT_TRI_SMALL, OPT_TRI_Q, OPT_NO_MR, OPT_MR_FORCE_BLUESTEIN, OPT_NO_ROWPQ,
   OPT_COLSOLVE, OPT_NO_LAT, OPT_F32_EPS_FLOOR, OPT_COLSTREAM_CHUNK, OPT_NO_ROWHALF, OPT_PAIR_MAXSIDE, OPT_ROWHALF_MINLG, OPT_NO_PQDCT,
-  OPT_NO_REORDER, OPT_NO_RAW, OPT_NO_TILEFUSE, OPT_NO_ROWPERS, OPT_NO_LFTILE, OPT_LF_ALL_ROUNDS, OPT_DFT_ENGINE, OPT_GAUSS_FFT_MINR, OPT_NO_GAUSS2D, OPT_NO_DFT_HALF, OPT_F32_STALL, OPT_PBS_LDS_PAD, OPT_NO_SHARED_PHASES, OPT_PA_STAG, OPT_PA_STAG_TICKS, OPT_PA_ROT, OPT_LF_STACK_BYTES, OPT_NO_YSPEC, OPT_COUNT
+  OPT_NO_REORDER, OPT_NO_RAW, OPT_NO_TILEFUSE, OPT_NO_ROWPERS, OPT_NO_LFTILE, OPT_LF_ALL_ROUNDS, OPT_DFT_ENGINE, OPT_GAUSS_FFT_MINR, OPT_NO_GAUSS2D, OPT_NO_DFT_HALF, OPT_F32_STALL, OPT_PBS_LDS_PAD, OPT_NO_SHARED_PHASES, OPT_PA_STAG, OPT_PA_STAG_TICKS, OPT_PA_ROT, OPT_LF_STACK_BYTES, OPT_NO_YSPEC, OPT_YSPEC_GROUP, OPT_COUNT
 };
 struct OptVal {
   bool set;
@@ -181,14 +181,15 @@ hipError_t launch_passA(int dtype, const Axis& a0, int n1, const void* image, co
                         int Bx, hipStream_t s, int nimg = 1);
 // The y-spectral form of pass A (periodic rows of 2048 / 4096 points): rowfft_kernel leaves Yhat = FFT_y(image -
 // mean) in the spectral register layout, passA_kernel filters its columns along x into Tbuf[plane][x][q] (= FFT_y of the
-// spatial plane, only the (plane, block of n1 / 16 positions) pairs listed), passA_strips_kernel the spatial columns within
+// spatial plane, only the (plane, block of n1 / 16 positions) pairs of the groups listed), passA_strips_kernel the spatial columns within
 // Epad of either row end into strips[plane][x][2 Epad] (first Epad: columns 0 .., last Epad: columns n1 - Epad ..).
 struct PassAYspec {
   void* Yhat;           // [nimg][n0][n1] complex
   void* strips;         // [nimg][Bx][n0][2 Epad] complex
-  const int* pairs;     // device [npairs]: plane | block << 16, ordered so that neighbours are different planes
-  int npairs;
-  unsigned blockmask;   // union of the blocks of all pairs: what the row pre-pass stores
+  const int* groups;    // device [ngroups][3]: block, first entry in `planes`, count (gpa_yspec.h: yspec_groups), largest first
+  const int* planes;    // device: the flat plane list the groups point into
+  int ngroups;
+  unsigned blockmask;   // union of the blocks of all groups: what the row pre-pass stores
   int E, Epad;
 };
 hipError_t launch_passA_yspec(int dtype, const Axis& a0, const Axis& a1, const void* image, const void* mean,

@@ -151,8 +151,9 @@ struct gpa_plan {
   // y-spectral sweep: pass A filters columns of FFT_y(image), pass B runs no forward transform
   bool ys_ok = false;             // the staged list / rows can take it (built with the shared tables)
   bool ys_use = false;            // ... and the sweep being staged does (sweep_choose_path; NO_YSPEC=1 keeps the spatial path)
-  PassAYspec ys{};                // Yhat / strips (grown on demand, ensure_yspec), the (plane, block) pairs of the staged list
-  int* d_ys_pairs = nullptr;      // [16 max_batch]
+  PassAYspec ys{};                // Yhat / strips (grown on demand, ensure_yspec), the (block, planes) groups of the staged list
+  int* d_ys_groups = nullptr;     // [16 max_batch][4]: the plane list (16 max_batch entries), behind it 3 ints per group
+  int ys_gmax = 0;                // the cap (YSPEC_GROUP) the staged groups were cut with
   size_t ys_yhat_bytes = 0, ys_strips_bytes = 0;
   std::vector<int> staged_planeof;
   void* Tbuf = nullptr;           // [tbuf_planes][n0][n1] complex: one plane per DISTINCT wx (x-plane), grown on demand

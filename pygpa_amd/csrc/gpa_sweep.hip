@@ -198,7 +198,8 @@ struct PassAGeom {
 // ---------------------------------------------------------------------------
 // MODE: PA_SPATIAL = the image's columns, every plane, into Tbuf.  PA_YSPEC = the same filter on columns q of
 // Yhat = FFT_y(image - mean) (complex input, rowfft_kernel): the x filter commutes with the transform along y, so this leaves
-// FFT_y(T_plane) for pass B to read; one (plane, tile) per workgroup, only the tiles inside the blocks a plane's peaks read.
+// FFT_y(T_plane) for pass B to read; one (group of planes, tile) per workgroup, only the tiles inside the blocks a plane's peaks
+// read.
 // PA_STRIPS = the spatial filter on the column tiles that cover [0, E) and [n1 - E, n1) alone, into the compact strips
 // buffer [plane][x][opitch = 2 Epad]: the samples the end fix of pass B multiplies, which FFT_y(T) does not give.
 enum { PA_SPATIAL = 0, PA_YSPEC = 1, PA_STRIPS = 2 };
@@ -209,8 +210,8 @@ __global__ __launch_bounds__((PassAGeom<T, LG>::THREADS)) void passA_kernel(
     const cpx<T>* __restrict__ wxr, int extL, int extR,
     const typename HType<PADDED, T>::type* __restrict__ H,
     const cpx<T>* __restrict__ twtab, cpx<T>* __restrict__ Tout, int B, int bchunk, int stag_phases, int stag_ticks,
-    int stag_first, int rot_mul, const cpx<T>* __restrict__ Yin, const int* __restrict__ pairs, int npairs, int ntl,
-    int opitch) {
+    int stag_first, int rot_mul, const cpx<T>* __restrict__ Yin, const int* __restrict__ groups,
+    const int* __restrict__ gplanes, int ntl, int opitch) {
   using F = WgFFT<T, LG>;
   using G = PassAGeom<T, LG>;
   constexpr int CT = G::CT, NT = G::NT, TPF = F::TPF, L = F::L;
@@ -233,16 +234,23 @@ __global__ __launch_bounds__((PassAGeom<T, LG>::THREADS)) void passA_kernel(
   }
   int y0 = tile * G::C + c * NT;   // first column of the thread (input)
   int oy0 = y0;                    // ... and where it goes in a row of the output
-  int plane = 0;                   // PA_YSPEC: the one plane of this workgroup
+  int gfirst = 0, gcount = 0, grot = 0;   // PA_YSPEC: the planes of this workgroup's group (entries of gplanes), its rotation
   const int op = MODE == PA_STRIPS ? opitch : n1;   // row pitch of the output
   if constexpr (MODE == PA_YSPEC) {
-    // tile -> (line of TPL tiles inside a block, (plane, block) pair, tile of the line), the pair varying faster than the
-    // line: the workgroups in flight on an XCD complete whole 128-byte lines and spread their row pieces over the planes
+    // A workgroup is one (group of planes that read a block, tile of C columns inside the block): it loads the tile once and
+    // filters it for every plane of the group.  Workgroup -> (XCD x, index idx on it) -> (group, line of TPL tiles, tile of the
+    // line): XCD x owns lines [x lpx, (x + 1) lpx) of every block and walks the groups in list order, i.e. largest first
+    // (yspec_groups), all its lines of one group before the next group.  So the TPL tiles that complete a 128-byte line are
+    // neighbours on one XCD, every XCD gets the same mix of long and short groups, and the short ones are the last to
+    // start: the tail of the grid is a short group's, not a long one's (the launcher checks that a block is 8 lpx lines).
     constexpr int TPL = (128 / (int)(G::C * sizeof(cpx<T>))) > 0 ? (128 / (int)(G::C * sizeof(cpx<T>))) : 1;
-    const int tl = tile % TPL, pr = (tile / TPL) % npairs, ln = tile / (TPL * npairs);
-    const int pe = pairs[pr];      // plane | block << 16
-    plane = pe & 0xffff;
-    y0 = (pe >> 16) * (n1 >> 4) + (ln * TPL + tl) * G::C + c * NT;
+    const int lpx = (n1 >> 7) / (G::C * TPL);
+    const int x = blockIdx.x & 7, idx = blockIdx.x >> 3;
+    const int tl = idx % TPL, ln = x * lpx + (idx / TPL) % lpx, g = idx / (TPL * lpx);
+    gfirst = groups[3 * g + 1];
+    gcount = groups[3 * g + 2];
+    grot = ln + g;
+    y0 = groups[3 * g] * (n1 >> 4) + (ln * TPL + tl) * G::C + c * NT;
     oy0 = y0;
   } else if constexpr (MODE == PA_STRIPS) {
     // tiles 0 .. ntl-1 cover the first, ntl .. 2 ntl - 1 the last ntl C columns; the last ones land behind the first Epad
@@ -258,21 +266,35 @@ __global__ __launch_bounds__((PassAGeom<T, LG>::THREADS)) void passA_kernel(
   T val[MODE == PA_YSPEC ? 1 : NT][16];
   cpx<T> cval[MODE == PA_YSPEC ? NT : 1][16];
   unsigned wrapmask = 0, rightmask = 0;   // slots of the left / right periodic extension (padded mode)
+  // PA_YSPEC: the thread's 16 rows of the tile of Yhat (n1 is a multiple of the tile and y0 of NT: the NT columns of the thread
+  // are one aligned load).  The tile stays in registers across the plane loop where 256 of them hold it beside the transforms
+  // without scratch: unpadded, up to 512 threads.  The other instantiations read it again for every plane of the group (cache
+  // hits after the first).  Unpadded, row t + TPF i is addressed as (uniform row-block pointer) + (one 32-bit offset of the
+  // thread), here and in the stores below: 16 + 16 row addresses of 64 bits do not fit beside a resident tile
+  // (profiles/passA_groups.txt).
+  constexpr bool KEEP = MODE == PA_YSPEC && !PADDED && G::THREADS <= 512;
+  const unsigned toff = (unsigned)t * (unsigned)n1 + (unsigned)y0;
+  auto load_tile = [&](unsigned off, int yc) {
+    struct alignas(NT * sizeof(cpx<T>)) Cols { cpx<T> v[NT]; };
+#pragma unroll
+    for (int i = 0; i < 16; ++i) {
+      const int xs = axis_src(t + TPF * i, n0, L, PADDED, extL, extR);
+      Cols cc;
+#pragma unroll
+      for (int n = 0; n < NT; ++n) cc.v[n] = {T(0), T(0)};
+      if constexpr (!PADDED) cc = *reinterpret_cast<const Cols*>(Yin + (size_t)(TPF * i) * n1 + off);
+      else if (xs >= 0) cc = *reinterpret_cast<const Cols*>(&Yin[(size_t)xs * n1 + yc]);
+#pragma unroll
+      for (int n = 0; n < (MODE == PA_YSPEC ? NT : 1); ++n) cval[n][i] = cc.v[n];
+    }
+  };
+  if constexpr (KEEP) load_tile(toff, y0);
 #pragma unroll
   for (int i = 0; i < 16; ++i) {
     const int slot = t + TPF * i;
     const int xs = axis_src(slot, n0, L, PADDED, extL, extR);
     if (PADDED && slot >= n0) { if (slot < n0 + extR) rightmask |= 1u << i; else wrapmask |= 1u << i; }
-    if constexpr (MODE == PA_YSPEC) {
-      // (n1 is a multiple of the tile and y0 of NT: the NT columns of the thread are one aligned load)
-      struct alignas(NT * sizeof(cpx<T>)) Cols { cpx<T> v[NT]; };
-      Cols cc;
-#pragma unroll
-      for (int n = 0; n < NT; ++n) cc.v[n] = {T(0), T(0)};
-      if (xs >= 0) cc = *reinterpret_cast<const Cols*>(&Yin[(size_t)xs * n1 + y0]);
-#pragma unroll
-      for (int n = 0; n < NT; ++n) cval[n][i] = cc.v[n];
-    } else {
+    if constexpr (MODE != PA_YSPEC) {
 #pragma unroll
       for (int n = 0; n < NT; ++n) {
         const int y = y0 + n;
@@ -297,16 +319,25 @@ __global__ __launch_bounds__((PassAGeom<T, LG>::THREADS)) void passA_kernel(
     __syncthreads();
   }
 
-  const int b0 = MODE == PA_YSPEC ? plane : blockIdx.y * bchunk;
-  const int b1 = MODE == PA_YSPEC ? plane + 1 : ((b0 + bchunk < B) ? b0 + bchunk : B);
+  // (PA_YSPEC: b walks the entries of the group, the plane is read from the list)
+  const int b0 = MODE == PA_YSPEC ? 0 : blockIdx.y * bchunk;
+  const int b1 = MODE == PA_YSPEC ? gcount : ((b0 + bchunk < B) ? b0 + bchunk : B);
   // plane rotation (PA_ROT=<m>, default 1 for transforms of 4096 points and more, 0 = off): the owners of line q start their
   // plane loop at plane (q m) mod nb.  The workgroups of this kernel run in step (one per CU, same work), so without it the whole
   // chip stores 32-byte row pieces of ONE plane at a time, 32 KB apart; spread over the planes (128 MB apart) the same stores
   // drain in 3.5 instead of 6.2 us per plane: 0.81 -> 0.68 ms at 4096^2 f32, 1.77 -> 1.61 f64 (profiles/r06_passA_rotation.txt).
-  // Every plane is computed exactly as before; only the order differs.
+  // Every plane is computed exactly as before; only the order differs.  (PA_YSPEC: inside the group, by line and group.)
   const int nb = b1 - b0;
-  int b = b0 + (nb > 0 ? (int)(((unsigned)(tile * G::C * (int)sizeof(cpx<T>) / 128) * (unsigned)rot_mul) % (unsigned)nb) : 0);
-  for (int j = 0; j < nb; ++j, b = (b + 1 < b1 ? b + 1 : b0)) {
+  const int rq = MODE == PA_YSPEC ? grot : tile * G::C * (int)sizeof(cpx<T>) / 128;
+  int bb = b0 + (nb > 0 ? (int)(((unsigned)rq * (unsigned)rot_mul) % (unsigned)nb) : 0);
+  for (int j = 0; j < nb; ++j, bb = (bb + 1 < b1 ? bb + 1 : b0)) {
+    const int b = MODE == PA_YSPEC ? gplanes[gfirst + bb] : bb;
+    if constexpr (MODE == PA_YSPEC && !KEEP) {
+      unsigned o = toff;   // (opaque: the loads and their 16 row addresses are not hoisted out of the loop)
+      int yc = y0;
+      asm volatile("" : "+v"(o), "+v"(yc));
+      load_tile(o, yc);
+    }
     F::refresh(tw);
     const cpx<T> base = cxb[(size_t)b * TPF + t];
     cpx<T> x[NT][16];
@@ -346,7 +377,8 @@ __global__ __launch_bounds__((PassAGeom<T, LG>::THREADS)) void passA_kernel(
           const int slot = t + TPF * i;
           if (!PADDED || slot < n0) {
             Pair pr = {x[0][i], x[1][i]};
-            *reinterpret_cast<Pair*>(&Tout[((size_t)b * n0 + slot) * op + oy0]) = pr;
+            if constexpr (MODE == PA_YSPEC && !PADDED) *reinterpret_cast<Pair*>(Tout + ((size_t)b * n0 + TPF * i) * n1 + toff) = pr;
+            else *reinterpret_cast<Pair*>(&Tout[((size_t)b * n0 + slot) * op + oy0]) = pr;
           }
         };
 #pragma unroll
@@ -361,7 +393,8 @@ __global__ __launch_bounds__((PassAGeom<T, LG>::THREADS)) void passA_kernel(
 #pragma unroll
           for (int i = 0; i < 16; ++i) {
             const int slot = t + TPF * i;
-            if (!PADDED || slot < n0) Tout[((size_t)b * n0 + slot) * op + oy0 + n] = x[n][i];
+            if constexpr (MODE == PA_YSPEC && !PADDED) Tout[((size_t)b * n0 + TPF * i) * n1 + toff + n] = x[n][i];
+            else if (!PADDED || slot < n0) Tout[((size_t)b * n0 + slot) * op + oy0 + n] = x[n][i];
           }
         }
       }
@@ -387,8 +420,9 @@ static hipError_t run_passA(const Axis& a0, int n1, const void* image, const voi
     int tiles = (n1 + G::C - 1) / G::C, ntl = 0, opitch = n1;
     if (MODE == PA_YSPEC) {
       // (a block of n1 / 16 columns is whole 128-byte lines of whole tiles: the kernel's tile map relies on it)
-      if (n1 % (16 * G::C) || ((size_t)(n1 / 16) * sizeof(cpx<T>)) % 128 || ys->npairs < 1) return hipErrorInvalidValue;
-      tiles = ys->npairs * (n1 / 16 / G::C);
+      constexpr int TPL = (128 / (int)(G::C * sizeof(cpx<T>))) > 0 ? (128 / (int)(G::C * sizeof(cpx<T>))) : 1;
+      if (n1 % (128 * G::C * TPL) || ((size_t)(n1 / 16) * sizeof(cpx<T>)) % 128 || ys->ngroups < 1) return hipErrorInvalidValue;
+      tiles = ys->ngroups * (n1 / 16 / G::C);
     } else if (MODE == PA_STRIPS) {
       ntl = (ys->E + G::C - 1) / G::C;
       opitch = 2 * ys->Epad;
@@ -410,7 +444,7 @@ static hipError_t run_passA(const Axis& a0, int n1, const void* image, const voi
         (const cpx<T>*)tb.wxw, (const cpx<T>*)tb.wxr, a0.extL, a0.extR,
         (const typename HType<PADDED, T>::type*)Hx, (const cpx<T>*)tw0, (cpx<T>*)(MODE == PA_STRIPS ? ys->strips : Tbuf), B, bchunk, stag,
         stag_ticks, device_cus(), opt_set(OPT_PA_ROT) ? (int)opt(OPT_PA_ROT).num : (LG >= 12 ? 1 : 0),
-        (const cpx<T>*)(ys ? ys->Yhat : nullptr), ys ? ys->pairs : nullptr, ys ? ys->npairs : 0, ntl, opitch);
+        (const cpx<T>*)(ys ? ys->Yhat : nullptr), ys ? ys->groups : nullptr, ys ? ys->planes : nullptr, ntl, opitch);
     return hipGetLastError();
   }
 }

@@ -11,6 +11,9 @@
 //     an even s is the register shift above, an odd s lands on thread t ^ 8, two registers further when t & 8.
 // GPA_HD: tests/host/yspec_emulator.cpp checks both against WgFFT::spec_index for every (s, t, i).
 #pragma once
+#include <algorithm>
+#include <vector>
+
 #include "gpa_fft.h"
 
 namespace gpa {
@@ -37,5 +40,42 @@ GPA_HD unsigned yspec_blockmask(int lg, int s, int nbl) {
   }
   return m;
 }
+
+// Pass A's work list: the (plane, block) pairs whose mask bit is set, gathered by block into groups of at most
+// gmax planes.  A workgroup of pass A loads a tile of Yhat once and filters it for every plane of its group, so a block read by
+// n planes is fetched ceil(n / gmax) times instead of n times; a block read by more than gmax planes is cut into full groups
+// and one remainder.  planes = the flat plane list, every group a contiguous run [first, first + count) of it, ascending.
+// The groups are ordered by count, largest first (ties: by block): pass A's tile map starts the groups of an XCD in list order,
+// so the long workgroups start first and the short ones fill the tail.  gmax = 1 gives the pairs themselves.
+struct YspecGroup { int block, first, count; };
+struct YspecGroups {
+  std::vector<YspecGroup> groups;
+  std::vector<int> planes;
+};
+
+inline YspecGroups yspec_groups(const unsigned* mask, int nplanes, int gmax) {
+  YspecGroups r;
+  if (gmax < 1) gmax = 1;
+  for (int blk = 0; blk < 16; ++blk) {
+    int run = 0;
+    for (int q = 0; q < nplanes; ++q) {
+      if (!((mask[q] >> blk) & 1)) continue;
+      if (run == 0 || run == gmax) { r.groups.push_back({blk, (int)r.planes.size(), 0}); run = 0; }
+      r.planes.push_back(q);
+      ++r.groups.back().count;
+      ++run;
+    }
+  }
+  std::stable_sort(r.groups.begin(), r.groups.end(), [](const YspecGroup& a, const YspecGroup& b) { return a.count > b.count; });
+  return r;
+}
+
+// The cap when YSPEC_GROUP is not set, measured at 4096^2, 3 peaks x 16 candidates (f32: blocks read by 12, 12, 4, 8, 12, 12, 12
+// planes), pass A in us, rocprofv3 average of 23 launches (profiles/passA_groups.txt):
+//   f32:  cap 1: 517   2: 360   3: 366   4: 312   6: 284   12: 313      (one plane per workgroup before the groups: 544)
+//   f64:  cap 4: 1270  6: 1293  12: 984                                 (before: 1725)
+// f32: an XCD's 32 CUs (one workgroup each) get 576 plane iterations; groups of 6 deal them out in 18 iterations' time, groups
+// of 4 in 20 (4.5 rounds), groups of 12 in 24 -- and the times follow.  f64 does best with one group per block.
+inline int yspec_group_default(int dtype) { return dtype == 0 ? 6 : 12; }
 
 }  // namespace gpa
