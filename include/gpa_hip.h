@@ -172,6 +172,10 @@ int gpa_unwrap_finish(gpa_plan* plan, int* iters_out);
 /* same from a wrapped phase image psi (phase_unwrap.py:141-208) */
 int gpa_unwrap(gpa_plan* plan, const void* psi, const void* weight, int kmax, double eps,
                int poisson_axes_compat, void* phi, int* iters_out);
+/* ... on device pointers (psi, weight, phi: n0 x n1 of the plan's dtype; phi must not overlap psi or weight).  Waits for
+ * the solve (the iteration count is its last word); gpa_unwrap is upload + this + download.                              */
+int gpa_unwrap_dev(gpa_plan* plan, const void* psi, const void* weight, int kmax, double eps,
+                   int poisson_axes_compat, void* phi, int* iters_out);
 
 /* fused driver: extract_displacement_field (geometric_phase_analysis.py:907-932,
  * deconvolve=False) with every intermediate kept in HBM.
@@ -387,6 +391,38 @@ int gpa_fit_plane(gpa_plan* plan, const void* image, int max_iter, double tol, d
                   int* iters_out);
 int gpa_fit_plane_dev(gpa_plan* plan, const void* image, int max_iter, double tol, double* coef3,
                       int* iters_out);
+/* the same fit of P contiguous planes of the plan's shape (device, P x n0 x n1; 1 <= P <= 65535): every IRLS round is one
+ * launch pair and one synchronisation for all planes that have not converged yet; a plane that has keeps its coefficients.
+ * coef: P x 3 and iters_out (nullable): P, host.  Plane q gets the coefficients and the pass count gpa_fit_plane_dev gives
+ * for it alone, bit for bit.                                                                                              */
+int gpa_fit_planes_dev(gpa_plan* plan, const void* images, int P, int max_iter, double tol, double* coef,
+                       int* iters_out);
+
+/* a8 -- iterate_GPA (geometric_phase_analysis.py:116-154) on device memory.
+ * gpa_lockin_polar_crop_dev: P lock-ins on the plan's n0 x n1 grid (device, complex) -> the window
+ * [edge : n0 - edge, edge : n1 - edge] as compact m0 x m1 planes (m = n - 2 edge): psi = angle, amp = |lock-in|, and, where
+ * weight is not NULL, weight = sqrt(amp / amax[p]).  amax (device, P reals of the plan's dtype) receives the maximum of
+ * amp[p] over the WINDOW (:141), whatever the order the workgroups finish in.  Enqueued on the plan's stream.              */
+int gpa_lockin_polar_crop_dev(gpa_plan* plan, const void* lockins, int P, int edge, void* psi, void* amp,
+                              void* weight, void* amax);
+/* The whole loop.  image: n0 x n1, its mean already subtracted by the caller as in the reference; kvecs: P x 2 (host);
+ * prs, w: P x m0 x m1 -- the unwrapped phases and the un-normalised amplitudes of the final pass; corr (P x 2), delta_ks
+ * (nullable, iters x P x 2: what each pass subtracted from corr) and unwrap_iters (nullable, (iters + 1) x P) are host
+ * memory.  plan has the frame's shape and max_batch >= P; crop_plan has the window's shape m0 x m1, the same dtype and
+ * device (edge = 0: plan itself, or NULL).  Each of the iters + 1 passes: lock-ins at kvecs + corr, polar crop, P weighted
+ * unwraps (kmax_iter iterations, kmax in the last pass; eps 1e-9, the reference's swapped-axis eigenvalues) and, except in
+ * the last pass, the Huber plane fits whose slopes / 2 pi are subtracted from corr -- in double on the host.  Inside a pass
+ * only the unwraps' iteration counts and the fits' sums come to the host.  Both forms return when everything is done.
+ * GPA_ERR_ARG names the offending argument; GPA_ERR_STATE says whether plan (a frame the sweep does not take) or crop_plan
+ * (a window without unwrap kernels) refuses -- nothing has been launched then.  With gpa_set_profiling on, gpa_last_stage_ms
+ * of plan gives [0] lock-ins [1] polar crop [2] unwraps [3] plane fits (wall time, every stage waited for).               */
+int gpa_iterate_gpa_dev(gpa_plan* plan, gpa_plan* crop_plan, const void* image, const double* kvecs, int P,
+                        double sigma, int edge, int iters, int kmax_iter, int kmax, void* prs, void* w,
+                        double* corr, double* delta_ks, int* unwrap_iters);
+/* image, prs, w in host memory */
+int gpa_iterate_gpa(gpa_plan* plan, gpa_plan* crop_plan, const void* image, const double* kvecs, int P,
+                    double sigma, int edge, int iters, int kmax_iter, int kmax, void* prs, void* w,
+                    double* corr, double* delta_ks, int* unwrap_iters);
 
 /* gaussian_deconvolve (geometric_phase_analysis.py:892-904) of ONE field: reflect-pad by 2 dr,
  * Wiener-Hunt deconvolution (skimage.restoration.wiener, Laplacian regulariser, `balance`) with the

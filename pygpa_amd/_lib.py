@@ -56,6 +56,7 @@ SIGNATURES = {
     'gpa_unwrap_prediff_enqueue_dev': (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _vp]),
     'gpa_unwrap_finish': (_i, [_vp, _vp]),
     'gpa_unwrap': (_i, [_vp, _vp, _vp, _i, _d, _i, _vp, _vp]),
+    'gpa_unwrap_dev': (_i, [_vp, _vp, _vp, _i, _d, _i, _vp, _vp]),
     'gpa_extract_displacement_field': (_i, [_vp, _vp, _vp, _i, _vp, _i, _d, _i, _i, _vp, _vp, _vp, _vp]),
     'gpa_extract_displacement_field_dev': (_i, [_vp, _vp, _vp, _i, _vp, _i, _d, _i, _i, _vp, _vp, _vp, _vp]),
     'gpa_extract_displacement_field_async': (_i, [_vp, _vp, _vp, _i, _vp, _i, _d, _i, _i, _vp, _vp, _vp]),
@@ -86,6 +87,10 @@ SIGNATURES = {
     'gpa_props_from_jac_dev': (_i, [_i, _i, _sz, _vp, _i, _d, _d, _i, _vp, _vp]),
     'gpa_fit_plane': (_i, [_vp, _vp, _i, _d, _dp, _ip]),
     'gpa_fit_plane_dev': (_i, [_vp, _vp, _i, _d, _dp, _ip]),
+    'gpa_fit_planes_dev': (_i, [_vp, _vp, _i, _i, _d, _vp, _vp]),
+    'gpa_lockin_polar_crop_dev': (_i, [_vp, _vp, _i, _i, _vp, _vp, _vp, _vp]),
+    'gpa_iterate_gpa_dev': (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
+    'gpa_iterate_gpa': (_i, [_vp, _vp, _vp, _vp, _i, _d, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'gpa_per_dft': (_i, [_vp, _vp, _vp]),
     'gpa_per_dft_dev': (_i, [_vp, _vp, _vp]),
     'gpa_per': (_i, [_vp, _vp, _i, _vp, _vp]),
@@ -542,6 +547,13 @@ class Plan:
                                           _ptr(kidx_ptr), _ptr(int(grad_ptr))),
               'gpa_sweep_grad_dev')
 
+    def lockin_batch_dev(self, image_ptr, kvecs, sigma, out_ptr):
+        """lockin_batch on device pointers: image n0 x n1 reals (its mean is NOT subtracted), out len(kvecs) x n0 x n1 complex;
+        enqueued on the plan's stream"""
+        kvecs = _f64(kvecs).reshape(-1, 2)
+        check(self.lib.gpa_lockin_batch_dev(self.handle, _ptr(int(image_ptr)), _ptr(kvecs), len(kvecs), float(sigma),
+                                            _ptr(int(out_ptr))), 'gpa_lockin_batch_dev')
+
     def lockin_weights_dev(self, lockins_ptr, P, weights_ptr):
         """np.abs of P lock-ins on the device"""
         check(self.lib.gpa_lockin_weights_dev(self.handle, _ptr(int(lockins_ptr)), int(P), _ptr(int(weights_ptr))),
@@ -575,6 +587,58 @@ class Plan:
         check(self.lib.gpa_fit_plane(self.handle, _ptr(image), int(max_iter), float(tol), coef, C.byref(iters)),
               'gpa_fit_plane')
         return np.array(coef[:]), iters.value
+
+    def fit_planes_dev(self, images_ptr, P, max_iter=200, tol=1e-12):
+        """fit_plane_dev of P contiguous plan-shaped planes on the device, one synchronisation per IRLS round for all of them:
+        (coef (P, 3), passes (P,)); plane q gets the bits fit_plane_dev gives for it alone"""
+        P = int(P)
+        coef = np.empty((P, 3), dtype=np.float64)
+        iters = np.zeros(P, dtype=np.int32)
+        check(self.lib.gpa_fit_planes_dev(self.handle, _ptr(int(images_ptr)), P, int(max_iter), float(tol), _ptr(coef), _ptr(iters)),
+              'gpa_fit_planes_dev')
+        return coef, iters
+
+    def lockin_polar_crop_dev(self, lockins_ptr, P, edge, psi_ptr, amp_ptr, amax_ptr, weight_ptr=None):
+        """P device lock-ins on the plan's grid -> np.angle / np.abs of the window [edge:-edge, edge:-edge] as compact planes
+        (psi, amp: P x m0 x m1 reals), amax (P reals) = amp[p].max() over the window, weight (optional) = sqrt(amp / amax[p]);
+        enqueued on the plan's stream"""
+        check(self.lib.gpa_lockin_polar_crop_dev(self.handle, _ptr(int(lockins_ptr)), int(P), int(edge), _ptr(int(psi_ptr)),
+                                                 _ptr(int(amp_ptr)), _ptr(weight_ptr), _ptr(int(amax_ptr))),
+              'gpa_lockin_polar_crop_dev')
+
+    def _iterate_args(self, kvecs, edge, iters, crop_plan):
+        """(kvecs (P, 2), P, window shape, crop handle, corr, delta_ks, unwrap_iters) of an iterate_gpa call"""
+        kvecs = _f64(kvecs).reshape(-1, 2)
+        P, edge, iters = len(kvecs), int(edge), int(iters)
+        if iters < 0 or edge < 0 or 2 * edge >= min(self.shape) - 1:
+            raise ValueError('iterate_gpa: need iters >= 0 and 0 <= 2 * edge < min(shape) - 1')
+        win = (self.shape[0] - 2 * edge, self.shape[1] - 2 * edge)
+        handle = None if crop_plan is None else crop_plan.handle
+        return (kvecs, P, win, handle, np.zeros((P, 2)), np.zeros((iters, P, 2)), np.zeros((iters + 1, P), dtype=np.int32))
+
+    def iterate_gpa(self, image, kvecs, sigma, edge=5, iters=3, kmax_iter=25, kmax=200, crop_plan=None):
+        """iterate_GPA of the reference in one library call (gpa_iterate_gpa).  image: the plan's shape, its mean already
+        subtracted; crop_plan: a Plan of the window's shape (n - 2 * edge per axis), the same dtype and device -- edge = 0
+        does without.  Returns (prs, w, corr, delta_ks, unwrap_iters): the final unwrapped phases and amplitudes
+        (P, m0, m1), the correction (P, 2), what each pass subtracted from it (iters, P, 2) and the unwraps' iteration
+        counts (iters + 1, P)."""
+        image = self._img(image)
+        kvecs, P, win, crop, corr, delta_ks, uit = self._iterate_args(kvecs, edge, iters, crop_plan)
+        prs = np.empty((P,) + win, dtype=self.rdtype)
+        w = np.empty((P,) + win, dtype=self.rdtype)
+        check(self.lib.gpa_iterate_gpa(self.handle, crop, _ptr(image), _ptr(kvecs), P, float(sigma), int(edge), int(iters),
+                                       int(kmax_iter), int(kmax), _ptr(prs), _ptr(w), _ptr(corr), _ptr(delta_ks), _ptr(uit)),
+              'gpa_iterate_gpa')
+        return prs, w, corr, delta_ks, uit
+
+    def iterate_gpa_dev(self, image_ptr, kvecs, sigma, prs_ptr, w_ptr, edge=5, iters=3, kmax_iter=25, kmax=200, crop_plan=None):
+        """iterate_gpa on device pointers: image n0 x n1, prs / w P x m0 x m1 of the plan's dtype.  Returns (corr, delta_ks,
+        unwrap_iters); the call has finished when it returns"""
+        kvecs, P, win, crop, corr, delta_ks, uit = self._iterate_args(kvecs, edge, iters, crop_plan)
+        check(self.lib.gpa_iterate_gpa_dev(self.handle, crop, _ptr(int(image_ptr)), _ptr(kvecs), P, float(sigma), int(edge),
+                                           int(iters), int(kmax_iter), int(kmax), _ptr(int(prs_ptr)), _ptr(int(w_ptr)),
+                                           _ptr(corr), _ptr(delta_ks), _ptr(uit)), 'gpa_iterate_gpa_dev')
+        return corr, delta_ks, uit
 
     def find_peaks(self, image, sigma, dog_sigma, threshold_rel, want_smooth=False, max_out=4096):
         """peak_local_max candidates of the smoothed spectrum: (coords (n, 2) int, values (n,)) sorted like
@@ -687,6 +751,14 @@ class Plan:
         check(self.lib.gpa_unwrap(self.handle, _ptr(psi), _ptr(w), int(kmax), float(eps), 1 if axes_compat else 0,
                                   _ptr(phi), C.byref(iters)), 'gpa_unwrap')
         return phi, iters.value
+
+    def unwrap_dev(self, psi_ptr, weight_ptr, phi_ptr, kmax=100, eps=1e-9, axes_compat=True):
+        """unwrap on device pointers (psi, weight or None, phi: plan-shaped, phi apart from the inputs); returns the iteration
+        count, i.e. waits for the solve"""
+        iters = C.c_int(0)
+        check(self.lib.gpa_unwrap_dev(self.handle, _ptr(int(psi_ptr)), _ptr(weight_ptr), int(kmax), float(eps),
+                                      1 if axes_compat else 0, _ptr(int(phi_ptr)), C.byref(iters)), 'gpa_unwrap_dev')
+        return iters.value
 
     def extract_displacement_field(self, image, kvecs, klists, sigma, mask_border, kmax=10,
                                    want_lockins=False, want_kidx=False, out=None, want_grads=False, want_weights=False,

@@ -268,6 +268,8 @@ void gpa_plan_destroy(gpa_plan* p) {
   if (p->d_pertab) (void)hipFree(p->d_pertab);
   if (p->d_peakws) (void)hipFree(p->d_peakws);
   if (p->d_peaksmooth) (void)hipFree(p->d_peaksmooth);
+  if (p->d_iter) (void)hipFree(p->d_iter);
+  if (p->h_iter) (void)hipHostFree(p->h_iter);
   if (p->h_k) hipHostFree(p->h_k);
   if (p->h_iters) hipHostFree(p->h_iters);
   if (p->kprof) {

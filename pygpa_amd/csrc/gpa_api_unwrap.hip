@@ -120,6 +120,19 @@ int gpa_unwrap_prediff(gpa_plan* p, const void* dx, const void* dy, const void* 
   return GPA_OK;
 }
 
+int gpa_unwrap_dev(gpa_plan* p, const void* psi, const void* weight, int kmax, double eps, int compat, void* phi,
+                   int* iters_out) {
+  if (!p || !psi || !phi) return fail(GPA_ERR_ARG, "gpa_unwrap: null argument");
+  if (kmax < 1) return fail(GPA_ERR_ARG, "gpa_unwrap: kmax must be >= 1");
+  NEED_UNWRAP(p, "gpa_unwrap");
+  HIP_TRY(hipSetDevice(p->device));
+  int iters = 0;
+  hipError_t e = unwrap_run(&p->uw, psi, nullptr, weight, true, kmax, eps, compat != 0, phi, &iters, p->stream);
+  if (e != hipSuccess) return unwrap_fail(e);
+  if (iters_out) *iters_out = iters;
+  return GPA_OK;
+}
+
 int gpa_unwrap(gpa_plan* p, const void* psi, const void* weight, int kmax, double eps, int compat, void* phi,
                int* iters_out) {
   if (!p || !psi || !phi) return fail(GPA_ERR_ARG, "gpa_unwrap: null argument");
@@ -129,11 +142,7 @@ int gpa_unwrap(gpa_plan* p, const void* psi, const void* weight, int kmax, doubl
   const size_t npx = (size_t)p->n0 * p->n1;
   HIP_TRY(hipMemcpyAsync(p->d_image, psi, npx * p->rsz, hipMemcpyHostToDevice, p->stream));
   if (weight) HIP_TRY(hipMemcpyAsync(p->d_wnorm, weight, npx * p->rsz, hipMemcpyHostToDevice, p->stream));
-  int iters = 0;
-  hipError_t e = unwrap_run(&p->uw, p->d_image, nullptr, weight ? p->d_wnorm : nullptr, true, kmax, eps,
-                            compat != 0, p->d_u, &iters, p->stream);
-  if (e != hipSuccess) return unwrap_fail(e);
-  if (iters_out) *iters_out = iters;
+  TRY(gpa_unwrap_dev(p, p->d_image, weight ? p->d_wnorm : nullptr, kmax, eps, compat, p->d_u, iters_out));
   HIP_TRY(hipMemcpyAsync(phi, p->d_u, npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   return GPA_OK;

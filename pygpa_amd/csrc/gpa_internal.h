@@ -263,6 +263,19 @@ int huber_sums_offset();
 hipError_t launch_huber_moments(int dtype, const void* img, int n0, int n1, const double* coef, double cx, double cy,
                                 double sx, double sy, double* scratch, hipStream_t s);
 
+// ---- a8 iterate_GPA (gpa_iterate.hip) ---------------------------------------------------------------------------------
+// P lock-ins (n0 x n1 complex) -> psi = angle, amp = |.| of the window [edge : n0 - edge, edge : n1 - edge] as compact planes;
+// amax[p] (device, of the real type, zeroed by the caller on s) = max of amp[p]
+hipError_t launch_polar_crop(int dtype, const void* lockins, int P, int n0, int n1, int edge, void* psi, void* amp,
+                             void* amax, hipStream_t s);
+// weight = sqrt(amp / amax[p]) of P planes of npx reals
+hipError_t launch_sqrt_norm(int dtype, const void* amp, int P, size_t npx, const void* amax, void* weight, hipStream_t s);
+// one IRLS pass of the Huber plane fit of P contiguous planes: state = 4 doubles per plane (coefficients, flag: 0 = skip the
+// plane), work = huber_batch_stride() doubles per plane, sums = ten doubles per plane
+size_t huber_batch_stride();
+hipError_t launch_huber_moments_batch(int dtype, const void* imgs, int P, int n0, int n1, const double* state, double cx,
+                                      double cy, double sx, double sy, double* work, double* sums, hipStream_t s);
+
 // ---- f-3 peak candidates (gpa_peaks.hip) --------------------------------------------------------
 constexpr int PEAK_PARTS = 1024;   // workgroups of the min / max reduction (2 doubles each)
 bool gauss2d_small_ok(int R);

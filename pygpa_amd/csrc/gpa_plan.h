@@ -223,6 +223,12 @@ struct gpa_plan {
   bool peaks_smooth_valid = false;
   WarpWs warp{};                  // scratch + taps of the Lawler-Fujita kernels (gpa_warp.hip), grown on first use
   UcellWs ucell{};                // scratch of unit-cell averaging / expansion (gpa_ucell.hip), grown on first use
+  // a8 iterate_GPA (gpa_api_iterate.hip), grown on demand: the Huber work of the batched plane fit, behind it the driver's
+  // amax / psi / weight planes (and the prs / w planes of its host form)
+  void* d_iter = nullptr;
+  size_t iter_bytes = 0;
+  double* h_iter = nullptr;       // pinned: per plane 4 doubles up (coefficients, flag), 10 down (sums)
+  size_t h_iter_planes = 0;
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool profiling = false;

@@ -18,6 +18,8 @@ hipError_t unwrap_workspace_create(int dtype, int n0, int n1, hipStream_t s, Unw
 void unwrap_workspace_destroy(UnwrapWorkspace* ws);
 // whether the workspace's image shape runs the fused iteration, the only one that takes several problems per launch
 bool unwrap_supports_batch(const UnwrapWorkspace* ws);
+// whether a solve on the workspace's image shape can start at all (false: unwrap_enqueue returns hipErrorNotSupported)
+bool unwrap_has_kernels(const UnwrapWorkspace* ws);
 
 // prediff == false: a = dx (n0 x (n1-1)), b = dy ((n0-1) x n1)
 // prediff == true : a = psi (n0 x n1), b ignored (differences taken on the device)

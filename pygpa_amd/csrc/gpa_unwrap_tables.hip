@@ -320,6 +320,11 @@ bool unwrap_supports_batch(const UnwrapWorkspace* ws) {
   return w && w->supported && (!w->generic || w->mr_ok);
 }
 
+bool unwrap_has_kernels(const UnwrapWorkspace* ws) {
+  const Impl* w = (const Impl*)ws->impl;
+  return w && w->supported;
+}
+
 void unwrap_workspace_destroy(UnwrapWorkspace* ws) {
   Impl* w = (Impl*)ws->impl;
   if (!w) return;

@@ -389,12 +389,45 @@ def fit_delta_k(phases):
     return fit_plane(phases)[:2] / (2 * np.pi)
 
 
-def iterate_GPA(image, kvecs, sigma, edge=5, iters=3, kmax_iter=25, kmax=200, verbose=False, dtype=None):
+def iterate_GPA(image, kvecs, sigma, edge=5, iters=3, kmax_iter=25, kmax=200, verbose=False, dtype=None, fused=True):
     """Iterate GPA, refining the reference vectors towards the extracted average
-    (geometric_phase_analysis.py:116-154).  Lock-ins and weighted unwraps run on the
-    device, including the 3-parameter Huber plane fit (gpa_fit_plane).
+    (geometric_phase_analysis.py:116-154).
+
+    fused=True (the default): one library call (gpa_iterate_gpa) -- lock-ins, phase / amplitude of the cropped maps,
+    weighted unwraps and the 3-parameter Huber plane fits stay on the device; per pass only the unwraps' iteration counts
+    and the fits' sums come to the host, which keeps the correction in float64.  fused=False: the same steps as a host
+    loop over the single entry points (lock-ins downloaded, np.angle / np.abs and the crop on the host, one upload per
+    unwrap and per fit), kept as the comparison partner.  ``verbose`` prints the delta_ks of every pass.
 
     Returns (prs, w, corr) like the reference."""
+    image = np.asarray(image)
+    kvecs = np.asarray(kvecs, dtype=np.float64)
+    if kvecs.shape == (2,):
+        kvecs = kvecs.reshape(1, 2)
+    if kvecs.ndim != 2 or kvecs.shape[1] != 2 or len(kvecs) < 1:
+        raise ValueError('kvecs must be (P, 2), not %s' % (kvecs.shape,))
+    if image.ndim != 2:
+        raise ValueError('image must be 2-D')
+    edge, iters = int(edge), int(iters)
+    if iters < 0:
+        raise ValueError('iters must be >= 0')
+    if edge < 0 or 2 * edge >= min(image.shape) - 1:
+        raise ValueError('edge = %d leaves no window of an image of shape %s' % (edge, image.shape))
+    if not fused:
+        return _iterate_GPA_host(image, kvecs, sigma, edge, iters, kmax_iter, kmax, verbose, dtype)
+    plan = _plan(image, len(kvecs), dtype)
+    window = (image.shape[0] - 2 * edge, image.shape[1] - 2 * edge)
+    crop_plan = plan if edge == 0 else _lib.get_plan(window, 1, DEFAULT_DTYPE if dtype is None else dtype)
+    prs, w, corr, delta_ks = plan.iterate_gpa(image, kvecs, sigma, edge=edge, iters=iters, kmax_iter=kmax_iter, kmax=kmax,
+                                              crop_plan=crop_plan)[:4]
+    if verbose:
+        for dk in delta_ks:
+            print(dk)
+    return prs, w, corr
+
+
+def _iterate_GPA_host(image, kvecs, sigma, edge, iters, kmax_iter, kmax, verbose, dtype):
+    """iterate_GPA as a host loop over lockin_batch, phase_unwrap and fit_plane (iterate_GPA(fused=False))"""
     from . import phase_unwrap as _pu
     image = np.asarray(image)
     kvecs = np.asarray(kvecs, dtype=np.float64).reshape(-1, 2)
