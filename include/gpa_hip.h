@@ -521,6 +521,16 @@ int gpa_last_stage_ms(gpa_plan* plan, float* ms5);
  * bracketed by HIP events on the stream it runs on; the two unwraps then run one after the other):
  * one text line "name launches total_ms" per kernel, NUL-terminated, into out[cap].              */
 int gpa_last_kernel_profile(gpa_plan* plan, char* out, size_t cap);
+/* The shared-forward pass B of the sweep skips a candidate on the rows where a spectral bound proves that it cannot
+ * win a pixel (same winners, bit for bit; gpa_set_option("NO_PB_SKIP", "1") switches the test off -- a
+ * diagnostic switch, not the kernel as it was before the test: the loop keeps its new shape and runs about 5 % longer).  Of the last such
+ * launch made with profiling on: the (row, candidate) pairs it skipped and all it visited (rows x candidates x peaks x
+ * images); both 0 when the last sweep of the plan was not profiled or took another kernel.  Waits for the stream.   */
+int gpa_last_passb_skips(gpa_plan* plan, long long* skipped, long long* visited);
+/* The order in which that kernel visits the K candidates of one peak (klist: K x 2, kref: 2): order_out[0 .. K) = list
+ * positions, x-planes (distinct wx) kept together, nearest to kref first; list order under NO_REORDER or for a list with two
+ * different k-vectors equal modulo whole cycles.  Host only: no plan, no device.                                       */
+int gpa_passb_visiting_order(const double* klist, const double* kref, int K, int* order_out);
 
 /* Download of a result while the GPU goes on with the next call: copies `bytes` from device memory
  * (e.g. the u of gpa_extract_displacement_field_async) to PAGE-LOCKED host memory on the plan's copy

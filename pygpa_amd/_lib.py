@@ -109,6 +109,8 @@ SIGNATURES = {
     'gpa_set_profiling': (_i, [_vp, _i]),
     'gpa_last_stage_ms': (_i, [_vp, _vp]),
     'gpa_last_kernel_profile': (_i, [_vp, C.c_char_p, _sz]),
+    'gpa_last_passb_skips': (_i, [_vp, _vp, _vp]),
+    'gpa_passb_visiting_order': (_i, [_vp, _vp, _i, _vp]),
     'gpa_download_async': (_i, [_vp, _vp, _vp, _sz, _i]),
     'gpa_download_wait': (_i, [_vp, _i]),
 }
@@ -157,6 +159,16 @@ def load():
             fn.argtypes = args
         _lib = lib
         return lib
+
+
+def passb_visiting_order(klist, kref):
+    """list positions of `klist` (K x 2) in the order the shared pass B visits them for the reference vector `kref`
+    (gpa_passb_visiting_order: the library's own rule, on the host)"""
+    kl = np.ascontiguousarray(klist, dtype=np.float64).reshape(-1, 2)
+    kr = np.ascontiguousarray(kref, dtype=np.float64).reshape(2)
+    out = np.empty(len(kl), dtype=np.int32)
+    check(load().gpa_passb_visiting_order(kl.ctypes.data, kr.ctypes.data, len(kl), out.ctypes.data), 'gpa_passb_visiting_order')
+    return [int(v) for v in out]
 
 
 def last_error():
@@ -1048,6 +1060,13 @@ class Plan:
             name, calls, ms = line.rsplit(' ', 2)
             out[name] = (int(calls), float(ms))
         return out
+
+    def last_passb_skips(self):
+        """(skipped, visited): the (row, candidate) pairs the shared pass B of the last profiled sweep skipped by its spectral
+        bound, and all it visited"""
+        sk, vi = C.c_longlong(0), C.c_longlong(0)
+        check(self.lib.gpa_last_passb_skips(self.handle, C.byref(sk), C.byref(vi)), 'gpa_last_passb_skips')
+        return sk.value, vi.value
 
     def download_async(self, host_array, dev_ptr, slot):
         """enqueue the D2H copy of host_array.nbytes from dev_ptr into the (page-locked) host_array"""

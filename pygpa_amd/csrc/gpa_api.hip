@@ -13,7 +13,7 @@ static const char* const kOptNames[OPT_COUNT] = {
     "PBS_FULLBAND", "SERIAL_UNWRAP", "NO_WORKER", "NO_KSPLIT", "NO_COMPACT", "NO_SHARED",
     "NO_PAIR", "TRI_SMALL", "TRI_Q", "NO_MR", "MR_FORCE_BLUESTEIN", "NO_ROWPQ", "COLSOLVE", "NO_LAT",
     "F32_EPS_FLOOR", "COLSTREAM_CHUNK", "NO_ROWHALF", "PAIR_MAXSIDE", "ROWHALF_MINLG", "NO_PQDCT",
-    "NO_REORDER", "NO_RAW", "NO_TILEFUSE", "NO_ROWPERS", "NO_LFTILE", "LF_ALL_ROUNDS", "DFT_ENGINE", "GAUSS_FFT_MINR", "NO_GAUSS2D", "NO_DFT_HALF", "F32_STALL", "PBS_LDS_PAD", "NO_SHARED_PHASES", "PA_STAG", "PA_STAG_TICKS", "PA_ROT", "LF_STACK_BYTES", "NO_YSPEC", "YSPEC_GROUP"};
+    "NO_REORDER", "NO_RAW", "NO_TILEFUSE", "NO_ROWPERS", "NO_LFTILE", "LF_ALL_ROUNDS", "DFT_ENGINE", "GAUSS_FFT_MINR", "NO_GAUSS2D", "NO_DFT_HALF", "F32_STALL", "PBS_LDS_PAD", "NO_SHARED_PHASES", "PA_STAG", "PA_STAG_TICKS", "PA_ROT", "LF_STACK_BYTES", "NO_YSPEC", "YSPEC_GROUP", "NO_PB_SKIP"};
 static OptVal g_opts[OPT_COUNT];
 static std::once_flag g_opts_once;
 static void opt_assign(OptVal& o, const char* value) {
@@ -239,7 +239,7 @@ void gpa_plan_destroy(gpa_plan* p) {
                   p->tb.dx, p->tb.dy, p->d_kl, p->d_kr, p->d_image, p->d_mean, p->d_tile_mean, p->d_scratch,
                   p->d_lockin, p->d_kidx, p->d_dudx, p->d_dudy, p->d_wnorm, p->d_u, p->d_kmat, p->d_sf, p->d_grad, p->d_grads, p->d_absw, p->d_aux0, p->d_aux1,
                   p->sh.Gb, p->sh.psi, p->sh.dyc, p->sh.gtab, p->sh.desc, p->sh.order, p->d_taps, p->tw1s,
-                  p->sh.pre, p->sh.rot16, p->d_wys, p->d_shifts, p->d_ystep, p->ys.Yhat, p->ys.strips, p->d_ys_groups};
+                  p->sh.pre, p->sh.rot16, p->d_wys, p->d_shifts, p->d_ystep, p->ys.Yhat, p->ys.strips, p->d_ys_groups, p->d_pbskip};
   for (void* b : bufs)
     if (b) hipFree(b);
   unwrap_workspace_destroy(&p->uw);
@@ -318,6 +318,18 @@ int gpa_timer_stop(gpa_plan* p, float* ms_out) {
 int gpa_set_profiling(gpa_plan* p, int on) {
   if (!p) return fail(GPA_ERR_ARG, "null plan");
   p->profiling = on != 0;
+  return GPA_OK;
+}
+int gpa_last_passb_skips(gpa_plan* p, long long* skipped, long long* visited) {
+  if (!p || !skipped || !visited) return fail(GPA_ERR_ARG, "gpa_last_passb_skips: null argument");
+  *skipped = *visited = 0;
+  if (!p->pbskip_valid) return GPA_OK;
+  HIP_TRY(hipSetDevice(p->device));
+  unsigned long long w[2] = {0, 0};
+  HIP_TRY(hipMemcpyAsync(w, p->d_pbskip, sizeof(w), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  *skipped = (long long)w[0];
+  *visited = (long long)w[1];
   return GPA_OK;
 }
 int gpa_last_kernel_profile(gpa_plan* p, char* out, size_t cap) {

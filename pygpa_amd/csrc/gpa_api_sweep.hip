@@ -84,6 +84,7 @@ int run_passA(gpa_plan* p, const void* image, const void* mean, void* Tbuf, int 
 // xp: the x-planes pass A left; a stack of images (the batched driver) has no split kernel and runs unsplit
 int passB_select(gpa_plan* p, const XPlanes& xp, int P, int K, void* lockin, int32_t* kidx, bool raw) {
   p->lk_raw = false;
+  p->pbskip_valid = false;
   const int rows_wg = (p->n0 + 7) / 8 * P;           // workgroups of the unsplit launch (at least: NF <= 8 rows each)
   int ksplit = 1;
   // (only while the unsplit launch has fewer workgroups than the chip has CUs: at 1024^2, 384 workgroups, the split
@@ -99,9 +100,15 @@ int passB_select(gpa_plan* p, const XPlanes& xp, int P, int K, void* lockin, int
     if (p->sh_use) {
       p->lk_raw = raw && !opt_set(OPT_NO_RAW) && p->sh_one_kref;
       const PassBYspec yb = {p->ys.strips, p->d_shifts};
+      // (profiling: the kernel counts the candidate rows its spectral bound skipped -- gpa_last_passb_skips)
+      p->pbskip_valid = p->profiling;
+      if (p->profiling) {
+        if (!p->d_pbskip) TRY(dmalloc(p, (void**)&p->d_pbskip, 2 * sizeof(unsigned long long)));
+        HIP_TRY(hipMemsetAsync(p->d_pbskip, 0, 2 * sizeof(unsigned long long), p->stream));
+      }
       HIP_TRY(launch_passB_shared(p->dtype, p->ax1s, p->n0, xp.T, p->ax1s.L == p->ax1.L ? p->tw1 : p->tw1s, p->tb,
                                   p->sh, p->sh_E, p->sh_Epad, P, K, lockin, kidx, p->stream, xp.nimg, xp.stride, p->sh_nbl,
-                                  p->lk_raw, ys ? &yb : nullptr));
+                                  p->lk_raw, ys ? &yb : nullptr, p->profiling ? p->d_pbskip : nullptr));
     } else
       HIP_TRY(launch_passB(p->dtype, p->ax1, p->n0, xp.T, p->Hy, p->tw1, p->tb, P, K, true, lockin, kidx, p->stream, xp.nimg,
                            xp.stride));

@@ -199,6 +199,58 @@ int ensure_filters(gpa_plan* p, double sigma) {
   return GPA_OK;
 }
 
+// The order in which the shared pass B visits the K candidates of one peak (kl, kr: K x 2 candidate / reference vectors,
+// planeof: the x-plane of every candidate, any non-negative labels) -> idx[0 .. K): list positions.  shared_prepare explains the
+// rule; gpa_passb_visiting_order exports it to the host (the NumPy model of the skip test visits in this very order).
+void passb_visiting_order(const double* kl, const double* kr, const int* planeof, int K, bool reorder, int* idx) {
+  bool aliased = false;
+  for (int a = 0; a < K && !aliased; ++a)
+    for (int b2 = a + 1; b2 < K && !aliased; ++b2) {
+      const double *ka = &kl[2 * a], *kb = &kl[2 * b2];
+      const bool same = ka[0] == kb[0] && ka[1] == kb[1];
+      aliased = !same && ka[0] - floor(ka[0]) == kb[0] - floor(kb[0]) && ka[1] - floor(ka[1]) == kb[1] - floor(kb[1]);
+    }
+  std::vector<double> d2((size_t)K), pmin;
+  std::vector<int> pfirst;
+  int nplanes = 0;
+  for (int k = 0; k < K; ++k) nplanes = std::max(nplanes, planeof[k] + 1);
+  pmin.assign((size_t)nplanes, 1e300);
+  pfirst.assign((size_t)nplanes, K);
+  for (int k = 0; k < K; ++k) {
+    const double ex = kl[2 * k] - kr[2 * k], ey = kl[2 * k + 1] - kr[2 * k + 1];
+    d2[k] = ex * ex + ey * ey;
+    const int pl = planeof[k];
+    pmin[pl] = std::min(pmin[pl], d2[k]);
+    pfirst[pl] = std::min(pfirst[pl], k);
+  }
+  for (int k = 0; k < K; ++k) idx[k] = k;
+  if (reorder && !aliased)
+    std::stable_sort(idx, idx + K, [&](int a, int b2) {
+      const int pa = planeof[a], pb = planeof[b2];
+      if (pa != pb) return pmin[pa] != pmin[pb] ? pmin[pa] < pmin[pb] : pfirst[pa] < pfirst[pb];
+      return d2[a] < d2[b2];
+    });
+}
+
+extern "C" int gpa_passb_visiting_order(const double* klist, const double* kref, int K, int* order_out) {
+  if (!klist || !kref || !order_out) return fail(GPA_ERR_ARG, "gpa_passb_visiting_order: null argument");
+  if (K < 1) return fail(GPA_ERR_ARG, "gpa_passb_visiting_order: K must be >= 1");
+  // x-planes as stage_kvectors maps them: one per distinct (bit-equal) wx, in order of first appearance
+  std::vector<int> planeof((size_t)K);
+  std::vector<double> kr(2 * (size_t)K);
+  int nplanes = 0;
+  for (int k = 0; k < K; ++k) {
+    int found = -1;
+    for (int q = 0; q < k && found < 0; ++q)
+      if (memcmp(&klist[2 * q], &klist[2 * k], sizeof(double)) == 0) found = planeof[q];
+    planeof[k] = found < 0 ? nplanes++ : found;
+    kr[2 * k] = kref[0];
+    kr[2 * k + 1] = kref[1];
+  }
+  passb_visiting_order(klist, kr.data(), planeof.data(), K, !opt_set(OPT_NO_REORDER), order_out);
+  return GPA_OK;
+}
+
 // candidate tables of the shared-forward pass B for the staged k-list (P peaks of K candidates): rebuilt when sigma
 // or the list changed.  Leaves p->sh_use = whether pass B should take that kernel for this (P, K).
 int shared_prepare(gpa_plan* p, int P, int K) {
@@ -236,35 +288,9 @@ int shared_prepare(gpa_plan* p, int P, int K) {
   // the two wins everywhere as the reference's rule says (round 6; tests/test_gpu_shared_passb.py::test_aliased_candidates_*).
   std::vector<int> order((size_t)B);
   for (int pp = 0; pp < P; ++pp) {
-    bool aliased = false;
-    for (int a = 0; a < K && !aliased; ++a)
-      for (int b2 = a + 1; b2 < K && !aliased; ++b2) {
-        const double *ka = &p->staged_kl[2 * ((size_t)pp * K + a)], *kb = &p->staged_kl[2 * ((size_t)pp * K + b2)];
-        const bool same = ka[0] == kb[0] && ka[1] == kb[1];
-        aliased = !same && ka[0] - floor(ka[0]) == kb[0] - floor(kb[0]) && ka[1] - floor(ka[1]) == kb[1] - floor(kb[1]);
-      }
-    std::vector<double> d2((size_t)K), pmin;
-    std::vector<int> pfirst;
-    int nplanes = 0;
-    for (int k = 0; k < K; ++k) nplanes = std::max(nplanes, p->staged_planeof[pp * K + k] + 1);
-    pmin.assign((size_t)nplanes, 1e300);
-    pfirst.assign((size_t)nplanes, K);
-    for (int k = 0; k < K; ++k) {
-      const size_t b = (size_t)pp * K + k;
-      const double ex = p->staged_kl[2 * b] - p->staged_kr[2 * b], ey = p->staged_kl[2 * b + 1] - p->staged_kr[2 * b + 1];
-      d2[k] = ex * ex + ey * ey;
-      const int pl = p->staged_planeof[b];
-      pmin[pl] = std::min(pmin[pl], d2[k]);
-      pfirst[pl] = std::min(pfirst[pl], k);
-    }
     std::vector<int> idx((size_t)K);
-    for (int k = 0; k < K; ++k) idx[k] = k;
-    if (reorder && !aliased)
-      std::stable_sort(idx.begin(), idx.end(), [&](int a, int b2) {
-        const int pa = p->staged_planeof[pp * K + a], pb = p->staged_planeof[pp * K + b2];
-        if (pa != pb) return pmin[pa] != pmin[pb] ? pmin[pa] < pmin[pb] : pfirst[pa] < pfirst[pb];
-        return d2[a] < d2[b2];
-      });
+    passb_visiting_order(&p->staged_kl[2 * (size_t)pp * K], &p->staged_kr[2 * (size_t)pp * K], &p->staged_planeof[(size_t)pp * K], K,
+                         reorder, idx.data());
     for (int k = 0; k < K; ++k) order[(size_t)pp * K + k] = pp * K + idx[k];
   }
   // runs of candidates on one x-plane, in visiting order; chunks of <= NC candidates per matrix pass

@@ -48,7 +48,11 @@ bool passB_yspec_supports(int dtype, const Axis& a1, int nbl);
 hipError_t launch_passB_shared(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* tw1, const SweepTables& tb,
                                const PassBSharedTables& st, int E, int Epad, int P, int K, void* out, int32_t* kidx,
                                hipStream_t s, int nimg = 1, int Bx = 0, int nbl = 16, bool raw = false,
-                               const PassBYspec* ys = nullptr);
+                               const PassBYspec* ys = nullptr, unsigned long long* skipcnt = nullptr);
+// A candidate whose spectral bound sum_k |X_k| |G_b(k)| cannot beat the running best anywhere on the rows of its workgroup is
+// skipped before its transform (same winners bit for bit; option NO_PB_SKIP=1 switches the test off: a diagnostic switch, the loop keeps its
+// new shape -- the chunk's contraction behind a barrier of its own -- and runs about 5 % longer than before the test).  skipcnt != null (device,
+// two words, zeroed by the caller on s): the kernel adds the candidate rows it skipped to [0] and those it visited to [1].
 hipError_t launch_passB_shared_phases(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* tw1, const SweepTables& tb,
                                       const PassBSharedTables& st, int E, int Epad, int P, int K, void* out, int32_t* kidx,
                                       void* psi_out, hipStream_t s, int Bx, int nbl, const PassBYspec* ys = nullptr);

@@ -107,6 +107,32 @@ __device__ __forceinline__ void store_cpx(cpx<double> v, __amdgpu_buffer_rsrc_t 
   __builtin_amdgcn_raw_buffer_store_b128(d, r, voff, soff, 0);
 }
 
+// ---- the skip test's sum over a wavefront: DPP inside a row of 16 lanes, four lane reads across the rows; one fixed
+// order, every lane gets the same bits ------------------------------------------------------------------------------
+template <int CTRL> __device__ __forceinline__ float dpp_get(float x) {
+  return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(x), CTRL, 0xf, 0xf, false));
+}
+template <int CTRL> __device__ __forceinline__ double dpp_get(double x) {
+  const int lo = __builtin_amdgcn_update_dpp(0, __double2loint(x), CTRL, 0xf, 0xf, false);
+  const int hi = __builtin_amdgcn_update_dpp(0, __double2hiint(x), CTRL, 0xf, 0xf, false);
+  return __hiloint2double(hi, lo);
+}
+__device__ __forceinline__ float lane_get(float x, int l) { return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(x), l)); }
+__device__ __forceinline__ double lane_get(double x, int l) {
+  return __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(x), l), __builtin_amdgcn_readlane(__double2loint(x), l));
+}
+// an upper bound of |c| up to the test's margin: f32 v_sqrt (within an ulp; squares that underflow lose < 1e-19, nothing
+// beside a t the test trusts only above 1e-15), f64 the cheaper |re| + |im|
+__device__ __forceinline__ float cmag(cpx<float> c) { return __builtin_amdgcn_sqrtf(c.x * c.x + c.y * c.y); }
+__device__ __forceinline__ double cmag(cpx<double> c) { return __builtin_elementwise_abs(c.x) + __builtin_elementwise_abs(c.y); }
+template <class T> __device__ __forceinline__ T wave_sum(T v) {
+  v += dpp_get<0xB1>(v);    // quad_perm [1, 0, 3, 2]
+  v += dpp_get<0x4E>(v);    // quad_perm [2, 3, 0, 1]
+  v += dpp_get<0x141>(v);   // row_half_mirror: the other quad of the eight
+  v += dpp_get<0x140>(v);   // row_mirror: the other eight of the row
+  return (lane_get(v, 0) + lane_get(v, 16)) + (lane_get(v, 32) + lane_get(v, 48));
+}
+
 // EE = elements per thread of the row transform: 16 in every instantiation (256 threads per 4096-point row, three passes).
 // (Eight per thread -- 512 threads, four passes, half the registers for one more exchange per transform -- measured slower
 //  and a tie on re-measurement: profiles/r03_passB_variants.txt, profiles/r05_sweep_variants.txt; git history has it.)
@@ -143,8 +169,11 @@ struct PassBSGeom {
     const size_t ES = (size_t)Epad + 4;
     return (size_t)F::LDS_ELEMS + SV * ES + 2 * NC * ES + (STAGE ? 3 * NC * ES : 0);
   }
+  // ... | Hankel taps | the skip test's words: 16 per-wavefront partial sums of the bound, 16 per-wavefront votes
+  static constexpr int SKIPW = 32;
+  static_assert(THREADS / 64 <= 16, "one partial sum and one vote per wavefront");
   __host__ __device__ static size_t lds_bytes(int Epad) {
-    return (NF * row_elems(Epad) + T1) * sizeof(cpx<T>) + (2 * (size_t)Epad + 16) * sizeof(T);
+    return (NF * row_elems(Epad) + T1) * sizeof(cpx<T>) + (2 * (size_t)Epad + 16 + SKIPW) * sizeof(T);
   }
 };
 
@@ -182,8 +211,24 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
     const cpx<T>* __restrict__ psi, const T* __restrict__ gtab, const cpx<T>* __restrict__ dx,
     const cpx<T>* __restrict__ dyc, const cpx<T>* __restrict__ rot16, int K, int E, int Epad, cpx<T>* out,
     int32_t* kidx, int P, int Bx, int raw, T* __restrict__ psi_out, const cpx<T>* __restrict__ strips_in,
-    const int* __restrict__ shifts) {
+    const int* __restrict__ shifts, int skip_on, unsigned long long* skipcnt) {
   static_assert(!YSPEC || (!PADDED && EE == 16 && NBL < EE), "y-spectral pass B: periodic rows, a rotated band");
+  // SKIP: a candidate whose row cannot beat the running best anywhere is dropped BEFORE its transform.
+  //   |y(j)| <= B_c = sum_k |X_k| |h_c(k)|   at every pixel j   (y = the inverse transform of X h_c; h holds G / L)
+  // (|X_k| is formed per candidate from the live registers -- cmag: f32 sqrt(Re^2 + Im^2), f64 the looser |Re| + |Im| --;
+  //  magnitudes kept per plane would save NBL square roots per candidate but cost NBL registers across the transform, 32
+  //  bytes of scratch at 4096 points in f32.  Measured at 4096^2, f32: the square root skips 50.7 % of the candidate rows
+  //  against 45.2 % with |Re| + |Im| and pass B runs 0.910 against 0.942 ms: profiles/passB_skip.txt)
+  // and the strict '>' of the selection can never hold where B_c^2 <= ab.  The kernel compares t = B_c (1 + 2^-10):
+  // the sum has non-negative terms (relative error <= (terms in a chain) eps ~ 20 eps), the magnitudes and the products
+  // a few eps more, and the computed transform differs from the exact one by O(eps log2 L) B_c ~ 50 eps B_c at most --
+  // together < 1e-4 B_c in f32, a tenth of the margin (far less in f64).  Squares below 1e-30 (denormal rounding is
+  // absolute, not relative) are not trusted: such a candidate runs.  A pixel within E of a row end also receives the
+  // Hankel correction: it compares (t + |correction| (1 + 2^-10))^2, the correction being the very number the fix-up
+  // adds.  Every comparison is written so that a NaN gives "run".  The phases form writes every candidate: no test.
+  // Nor do the f64 instantiations of the spatial form (zero-padded rows, NO_YSPEC) carry it: they have no registers for it
+  // (scratch 32 -> 272 bytes on zero-padded 4096-point rows); f64 rows of 2048 / 4096 points take the y-spectral form.
+  constexpr bool SKIP = !PSI && (sizeof(T) == 4 || YSPEC);
   using F = WgFFT<T, LG, EE>;
   using G = PassBSGeom<T, LG, EE>;
   using V4 = typename MfmaVec<T>::type;
@@ -200,13 +245,19 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
   cpx<T>* psi_l = pre_l + NC * ES;               // [2][NC][ES]    (STAGE)
   cpx<T>* t1 = reinterpret_cast<cpx<T>*>(smem) + (size_t)G::NF * G::row_elems(Epad);
   T* glds = reinterpret_cast<T*>(t1 + G::T1);
+  T* bsum = glds + 2 * Epad + 16;                       // [wavefront] partial sums of the bound
+  int* vote = reinterpret_cast<int*>(bsum + 16);        // [wavefront] 1 = some lane of it could win
+  constexpr int WAVES = G::THREADS / 64;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  int nskip = 0;
   const int row = blockIdx.x * G::NF + f;
   const bool valid = row < n0;
   const int rr = valid ? row : 0;
   const int p = blockIdx.y, pt = p % P, img = p / P;
   const int lane = threadIdx.x & 63, wrow = tid >> 6;
 
-  // Hankel taps g(1 .. E) (zero beyond) and the pass-1 twiddles: first read after the barriers of the first transform
+  // Hankel taps g(1 .. E) (zero beyond): first read by the contraction -- with the skip test behind the contraction's own
+  // barrier, without it after the first barrier of the first transform
   for (int i = threadIdx.x; i < 2 * Epad + 16; i += G::THREADS) glds[i] = gtab[i];
   // (pass-1 twiddles: from the LDS table where registers are short -- f64, zero-padded rows -- and in registers for
   //  periodic f32 rows, which have had 20 registers to spare at 3 waves per SIMD since the winner stores became rare:
@@ -221,9 +272,11 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
     F::load_twiddles(tw, twtab, tid);
   }
 
+  // (zero-padded rows: the slots beyond the row never store and must not keep a candidate alive either)
   T ab[EE];
+  T abmin = T(0);   // the smallest of them, kept up to date by the selection: what the skip test compares with
 #pragma unroll
-  for (int i = 0; i < EE; ++i) ab[i] = T(0);
+  for (int i = 0; i < EE; ++i) ab[i] = (PADDED && SKIP && tid + TPF * i >= n1) ? T(INFINITY) : T(0);
   const size_t obase = ((size_t)p * n0 + rr) * n1;
   // the winner's row as a buffer: a lane that does not win (or lies beyond the image) stores to an out-of-range
   // offset, which the hardware drops -- sixteen predicated stores per candidate without a branch
@@ -314,36 +367,26 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
     }
     // ---- candidate b: shifted Gaussian, inverse transform (the matrix pass of a new chunk rides between its barriers)
     const int par = (d >> 7) & 1;   // parity of the chunk: which copy of the staged post-factors this candidate reads
-    cpx<T> y[EE];
-    {
-      if (!PREFETCH || k == 0) load_gb<T, TPF, NBL>(h, Gb + (size_t)b * (NBL * TPF), tid);
-      if constexpr (STAGE) {
-        if (d & 2) {
-          // phasors of this chunk's candidates into LDS: exp(2 pi i wy j) (strip pre-factors) and the post-factors
-          const int nc = (d >> 4) & 7;
-          for (int e = tid; e < NC * Epad; e += TPF) {
-            const int c = e / Epad, j = e - c * Epad, cc = c < nc ? c : nc - 1;
-            pre_l[c * ES + j] = pre_g[(size_t)(b + cc) * Epad + j];
-            psi_l[(par * NC + c) * ES + j] = psi[(size_t)(b + cc) * Epad + j];
-          }
+    if (!PREFETCH || k == 0) load_gb<T, TPF, NBL>(h, Gb + (size_t)b * (NBL * TPF), tid);
+    if constexpr (STAGE) {
+      if (d & 2) {
+        // phasors of this chunk's candidates into LDS: exp(2 pi i wy j) (strip pre-factors) and the post-factors
+        const int nc = (d >> 4) & 7;
+        for (int e = tid; e < NC * Epad; e += TPF) {
+          const int c = e / Epad, j = e - c * Epad, cc = c < nc ? c : nc - 1;
+          pre_l[c * ES + j] = pre_g[(size_t)(b + cc) * Epad + j];
+          psi_l[(par * NC + c) * ES + j] = psi[(size_t)(b + cc) * Epad + j];
         }
-      }
-#pragma unroll
-      for (int i = 0; i < EE; ++i) {
-        if (i < NBL) y[i] = {X[i < NBL ? i : 0].x * h[i < NBL ? i : 0], X[i < NBL ? i : 0].y * h[i < NBL ? i : 0]};
-        else y[i] = {T(0), T(0)};
       }
     }
     cpx<T> psL = {T(0), T(0)}, psR = {T(0), T(0)};
     const int a0R = PADDED ? 0 : TPF - 1 - tid;
     if constexpr (!STAGE) {
-      // post-factors of the end fix, requested now, used after the transform
+      // post-factors of the end fix, requested now, used by the skip test and after the transform
       psL = psi[(size_t)b * Epad + (tid < E ? tid : 0)];
       psR = psi[(size_t)b * Epad + (a0R < E ? a0R : 0)];
     }
-    F::template inv_phase<0>(y, lds, tid, tw);
-    __syncthreads();
-    if (d & 2) {
+    auto contract = [&]() {
       // end-fix contraction for the candidates b .. b + nc - 1: D[a][n] = sum_j g(a + 1 + j) B[j][n], column
       // n = (end, candidate, re/im).  Lane l supplies A[l & 15][l >> 4] and B[l >> 4][l & 15] of each k-step.
       const int nc = (d >> 4) & 7;
@@ -392,60 +435,185 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
           }
         }
       }
-    }
-    F::template inv_phase<1>(y, lds, tid, tw);
-    __syncthreads();
-    F::template inv_phase<2>(y, lds, tid, tw);
-    if constexpr (F::P == 4) {
-      __syncthreads();
-      F::template inv_phase<3>(y, lds, tid, tw);
-    }
-    // ---- the outputs within E of either end get their wrapped pairs ------------------------------------------
-    {
+    };
+    // the end corrections of this candidate (zero where the lane has none): cL for y[0] (tid < E); cA for the register
+    // that holds the row's last samples -- y[EE - 1] (a0R < E) of a periodic row, register iA of a zero-padded one, where
+    // they may straddle into iB = iA + 1 (wave-uniform): cB
+    auto corrections = [&](int tid, cpx<T>& cL, cpx<T>& cA, cpx<T>& cB) {
+      const int a0R = PADDED ? 0 : TPF - 1 - tid;
       const int c = (d >> 2) & 3;
       const cpx<T>* pl = psi_l + (par * NC + c) * ES;
+      cL = cA = cB = cpx<T>{T(0), T(0)};
       if (tid < E) {
         const cpx<T> fx = fixb[(c * 2 + 1) * ES + tid];
-        if constexpr (STAGE) psL = pl[tid];
-        const cpx<T> t = cmulc(fx, psL);
-        y[0].x += t.x;
-        y[0].y += t.y;
+        cL = cmulc(fx, STAGE ? pl[tid] : psL);
       }
       if constexpr (!PADDED) {
         if (a0R < E) {
           const cpx<T> fx = fixb[(c * 2 + 0) * ES + a0R];
-          if constexpr (STAGE) psR = pl[a0R];
-          const cpx<T> t = cmul(fx, psR);
-          y[EE - 1].x += t.x;
-          y[EE - 1].y += t.y;
+          cA = cmul(fx, STAGE ? pl[a0R] : psR);
         }
       } else {
-        // zero-padded rows: the last E samples sit in register iA and, where they straddle a register, iB = iA + 1
-        // (wave-uniform): the two possible corrections are formed without touching y, then added to whichever
-        // register holds them under scalar branches
-        cpx<T> fA = {T(0), T(0)}, fB = {T(0), T(0)};
-        {
-          const int aA = n1 - 1 - (tid + TPF * iA), aB = aA - TPF;
-          const bool inA = aA >= 0 && aA < E, inB = aB >= 0 && aB < E && iB != iA;
-          const int qa = inA ? aA : 0, qb = inB ? aB : 0;
-          const cpx<T> xa = fixb[(c * 2 + 0) * ES + qa], xb = fixb[(c * 2 + 0) * ES + qb];
-          const cpx<T> pa = STAGE ? pl[qa] : psi[(size_t)b * Epad + qa], pb = STAGE ? pl[qb] : psi[(size_t)b * Epad + qb];
-          const cpx<T> ta = cmul(xa, pa), tb2 = cmul(xb, pb);
-          fA = {inA ? ta.x : T(0), inA ? ta.y : T(0)};
-          fB = {inB ? tb2.x : T(0), inB ? tb2.y : T(0)};
-        }
+        const int aA = n1 - 1 - (tid + TPF * iA), aB = aA - TPF;
+        const bool inA = aA >= 0 && aA < E, inB = aB >= 0 && aB < E && iB != iA;
+        const int qa = inA ? aA : 0, qb = inB ? aB : 0;
+        const cpx<T> xa = fixb[(c * 2 + 0) * ES + qa], xb = fixb[(c * 2 + 0) * ES + qb];
+        const cpx<T> pa = STAGE ? pl[qa] : psi[(size_t)b * Epad + qa], pb = STAGE ? pl[qb] : psi[(size_t)b * Epad + qb];
+        const cpx<T> ta = cmul(xa, pa), tb2 = cmul(xb, pb);
+        cA = {inA ? ta.x : T(0), inA ? ta.y : T(0)};
+        cB = {inB ? tb2.x : T(0), inB ? tb2.y : T(0)};
+      }
+    };
+    bool runs = true;   // workgroup-uniform
+    if constexpr (SKIP) {
+      // The contraction of a chunk runs at the chunk's start, before the first test that reads its results, whether or not
+      // that candidate is then skipped.  (The barrier: the strips and the staged phasors are in LDS, and nobody still
+      // reads the previous chunk's results.  Without the test -- the phases form -- it rides between two barriers of the
+      // chunk's first transform.)
+      if (d & 2) {
+        __syncthreads();
+        contract();
+      }
+      // the first visited candidate of a peak (ab = 0) always runs
+      if (skip_on && k > 0) {
+        T part = T(0);
 #pragma unroll
-        for (int i = 0; i < EE; ++i) {
-          if (i == iA) { y[i].x += fA.x; y[i].y += fA.y; }
-          if (i == iB && iB != iA) { y[i].x += fB.x; y[i].y += fB.y; }
+        for (int i = 0; i < NBL; ++i)
+          part += cmag(X[i]) * __builtin_elementwise_abs(h[i]);
+        part = wave_sum(part);
+        if (lane == 0) bsum[wave] = part;
+        __syncthreads();
+        // B_c of this thread's row: its wavefronts' sums in a fixed order, the same bits in every thread of the row
+        T bc = T(0);
+#pragma unroll
+        for (int w = 0; w < G::NW; ++w) bc += bsum[f * G::NW + w];
+        constexpr T MARGIN = T(1) + T(1) / T(1024);
+        const T t = bc * MARGIN, t2 = t * t;
+        // (the test's addresses hang on a copy of the thread index the compiler cannot see through: shared with the
+        //  fix-up's they would stay in registers across the whole transform)
+        int tid_t = tid;
+        asm volatile("" : "+v"(tid_t));
+        cpx<T> cL, cA, cB;
+        corrections(tid_t, cL, cA, cB);
+        const T tL = t + cmag(cL) * MARGIN, tA = t + cmag(cA) * MARGIN;
+        // safe = no pixel of this thread can win; every comparison is false on a NaN, which keeps the candidate
+        bool safe = t2 >= T(1e-30) && t2 <= abmin && tL * tL <= ab[0];
+        if constexpr (!PADDED) {
+          safe = safe && tA * tA <= ab[EE - 1];
+        } else {
+          const T tB = t + cmag(cB) * MARGIN;
+#pragma unroll
+          for (int i = 0; i < EE; ++i) {
+            if (i == iA) safe = safe && tA * tA <= ab[i];
+            if (i == iB && iB != iA) safe = safe && tB * tB <= ab[i];
+          }
+        }
+        const bool wave_runs = __builtin_amdgcn_ballot_w64(!safe) != 0;
+        if (lane == 0) vote[wave] = wave_runs ? 1 : 0;
+        __syncthreads();
+        // skipped only if no thread of any row of the workgroup could win: the branch is workgroup-uniform
+        int run = 0;
+#pragma unroll
+        for (int w = 0; w < WAVES; ++w) run |= vote[w];
+        runs = __builtin_amdgcn_readfirstlane(run) != 0;
+      }
+    }
+    // (a skipped candidate still requests the next candidate's Gaussian below -- ONE request site for both paths, or the
+    //  compiler merges two register sets with copies that wait for the loads -- and the next plane at the loop's top)
+    if constexpr (!PREFETCH) {
+      if (!runs) {
+        ++nskip;
+        continue;
+      }
+    }
+    cpx<T> y[EE];
+    if (runs) {
+#pragma unroll
+      for (int i = 0; i < EE; ++i) {
+        if (i < NBL) y[i] = {X[i < NBL ? i : 0].x * h[i < NBL ? i : 0], X[i < NBL ? i : 0].y * h[i < NBL ? i : 0]};
+        else y[i] = {T(0), T(0)};
+      }
+      F::template inv_phase<0>(y, lds, tid, tw);
+      __syncthreads();
+      if constexpr (!SKIP) {
+        if (d & 2) contract();
+      }
+      F::template inv_phase<1>(y, lds, tid, tw);
+      __syncthreads();
+      F::template inv_phase<2>(y, lds, tid, tw);
+      if constexpr (F::P == 4) {
+        __syncthreads();
+        F::template inv_phase<3>(y, lds, tid, tw);
+      }
+      // ---- the outputs within E of either end get their wrapped pairs ------------------------------------------
+      if constexpr (!SKIP) {
+        // (the instantiations without the test keep the fix-up as it was: formed where it is added)
+        const int c = (d >> 2) & 3;
+        const cpx<T>* pl = psi_l + (par * NC + c) * ES;
+        if (tid < E) {
+          const cpx<T> fx = fixb[(c * 2 + 1) * ES + tid];
+          if constexpr (STAGE) psL = pl[tid];
+          const cpx<T> t = cmulc(fx, psL);
+          y[0].x += t.x;
+          y[0].y += t.y;
+        }
+        if constexpr (!PADDED) {
+          if (a0R < E) {
+            const cpx<T> fx = fixb[(c * 2 + 0) * ES + a0R];
+            if constexpr (STAGE) psR = pl[a0R];
+            const cpx<T> t = cmul(fx, psR);
+            y[EE - 1].x += t.x;
+            y[EE - 1].y += t.y;
+          }
+        } else {
+          cpx<T> fA = {T(0), T(0)}, fB = {T(0), T(0)};
+          {
+            const int aA = n1 - 1 - (tid + TPF * iA), aB = aA - TPF;
+            const bool inA = aA >= 0 && aA < E, inB = aB >= 0 && aB < E && iB != iA;
+            const int qa = inA ? aA : 0, qb = inB ? aB : 0;
+            const cpx<T> xa = fixb[(c * 2 + 0) * ES + qa], xb = fixb[(c * 2 + 0) * ES + qb];
+            const cpx<T> pa = STAGE ? pl[qa] : psi[(size_t)b * Epad + qa], pb = STAGE ? pl[qb] : psi[(size_t)b * Epad + qb];
+            const cpx<T> ta = cmul(xa, pa), tb2 = cmul(xb, pb);
+            fA = {inA ? ta.x : T(0), inA ? ta.y : T(0)};
+            fB = {inB ? tb2.x : T(0), inB ? tb2.y : T(0)};
+          }
+#pragma unroll
+          for (int i = 0; i < EE; ++i) {
+            if (i == iA) { y[i].x += fA.x; y[i].y += fA.y; }
+            if (i == iB && iB != iA) { y[i].x += fB.x; y[i].y += fB.y; }
+          }
+        }
+      } else
+      {
+        cpx<T> cL, cA, cB;
+        corrections(tid, cL, cA, cB);
+        if (tid < E) {
+          y[0].x += cL.x;
+          y[0].y += cL.y;
+        }
+        if constexpr (!PADDED) {
+          if (a0R < E) {
+            y[EE - 1].x += cA.x;
+            y[EE - 1].y += cA.y;
+          }
+        } else {
+          // (added to whichever register holds them under scalar branches)
+#pragma unroll
+          for (int i = 0; i < EE; ++i) {
+            if (i == iA) { y[i].x += cA.x; y[i].y += cA.y; }
+            if (i == iB && iB != iA) { y[i].x += cB.x; y[i].y += cB.y; }
+          }
         }
       }
+    } else {
+      ++nskip;
     }
     // the next candidate's Gaussian (NBL values) is requested BEFORE this candidate's stores: vmcnt counts loads and
     // stores in order, so loads issued behind the stores would wait for the stores' acknowledgements as well
     if constexpr (PREFETCH) {
       if (k + 1 < K) load_gb<T, TPF, NBL>(h, Gb + (size_t)(b + 1) * (NBL * TPF), tid);
     }
+    if (!runs) continue;
     const int kout = ob - pt * K;
     if constexpr (PSI) {
       if (valid) {
@@ -466,6 +634,7 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
       const T a = y[i].x * y[i].x + y[i].y * y[i].y;
       const bool win = a > ab[i];
       ab[i] = win ? a : ab[i];
+      if constexpr (SKIP) abmin = i == 0 ? ab[0] : fmin(abmin, ab[i]);   // (ab holds no NaN: a NaN never wins)
       if (__builtin_amdgcn_ballot_w64(win) == 0) continue;
       // (byte offset; OOB = 0x80000000 stays out of range after the arithmetic shift below, never multiply it)
       // (zero-padded rows: the whole column offset goes into the range-checked voffset, so that the slots beyond
@@ -476,6 +645,12 @@ __global__ __launch_bounds__((PassBSGeom<T, LG, EE>::THREADS),
       constexpr int SH = sizeof(cpx<T>) == 8 ? 1 : 2;   // complex byte offset -> int32 byte offset
       if (kidx) __builtin_amdgcn_raw_buffer_store_b32(kout, krow, woff >> SH, SOFF * i * TPF * 4, 0);
     }
+  }
+  // (profiling only: candidate rows skipped / visited by this workgroup)
+  if (skipcnt && threadIdx.x == 0) {
+    const int rows = n0 - blockIdx.x * G::NF < G::NF ? n0 - blockIdx.x * G::NF : G::NF;
+    atomicAdd(skipcnt, (unsigned long long)nskip * rows);
+    atomicAdd(skipcnt + 1, (unsigned long long)K * rows);
   }
   if (!valid) return;
   if (raw) {
@@ -603,7 +778,7 @@ template <class T, int LG, bool PADDED, int EE, int NBL, bool PSI = false, bool 
 static hipError_t run_passB_shared(const Axis& a1, int n0, const void* Tbuf, const void* tw1, const SweepTables& tb,
                                    const PassBSharedTables& st, int E, int Epad, int P, int K, void* out, int32_t* kidx,
                                    hipStream_t s, int nimg, int Bx, bool raw, void* psi_out = nullptr,
-                                   const PassBYspec* ys = nullptr) {
+                                   const PassBYspec* ys = nullptr, unsigned long long* skipcnt = nullptr) {
   if (YSPEC && (!ys || !ys->strips || !ys->shifts)) return hipErrorInvalidValue;
   using G = PassBSGeom<T, LG, EE>;
   size_t lds = G::lds_bytes(Epad);
@@ -626,7 +801,8 @@ static hipError_t run_passB_shared(const Axis& a1, int n0, const void* Tbuf, con
   kern<<<grid, G::THREADS, lds, s>>>((const cpx<T>*)Tbuf, n0, a1.n, (const T*)st.Gb, (const cpx<T>*)tw1, tb.planeof, st.order, st.desc,
                                      (const cpx<T>*)st.pre, (const cpx<T>*)st.psi, (const T*)st.gtab, (const cpx<T>*)tb.dx,
                                      (const cpx<T>*)st.dyc, (const cpx<T>*)st.rot16, K, E, Epad, (cpx<T>*)out, kidx, P, Bx, raw ? 1 : 0, (T*)psi_out,
-                                     (const cpx<T>*)(YSPEC ? ys->strips : nullptr), YSPEC ? ys->shifts : nullptr);
+                                     (const cpx<T>*)(YSPEC ? ys->strips : nullptr), YSPEC ? ys->shifts : nullptr,
+                                     opt_set(OPT_NO_PB_SKIP) ? 0 : 1, PSI ? nullptr : skipcnt);
   return hipGetLastError();
 }
 
@@ -644,7 +820,7 @@ bool passB_shared_supports(int dtype, const Axis& a1, int E) {
   const size_t ES = (size_t)Epad + 4;
   const size_t stage = dtype == 0 ? 3 * nc * ES : 0;
   const size_t lds = (nf * ((size_t)(a1.L + a1.L / 16) + (dtype == 0 ? 4 : 2) * ES + 2 * nc * ES + stage) + 16 * 6) * csz +
-                     (2 * (size_t)Epad + 16) * (csz / 2);
+                     (2 * (size_t)Epad + 16 + 32) * (csz / 2);   // (+ the skip test's words: PassBSGeom::SKIPW)
   return lds <= 160 * 1024;
 }
 
@@ -693,19 +869,20 @@ hipError_t launch_passB_shared_phases(int dtype, const Axis& a1, int n0, const v
 
 hipError_t launch_passB_shared(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* tw1, const SweepTables& tb,
                                const PassBSharedTables& st, int E, int Epad, int P, int K, void* out, int32_t* kidx,
-                               hipStream_t s, int nimg, int Bx, int nbl, bool raw, const PassBYspec* ys) {
+                               hipStream_t s, int nimg, int Bx, int nbl, bool raw, const PassBYspec* ys,
+                               unsigned long long* skipcnt) {
   if (ys) {
     if (a1.padded) return hipErrorInvalidValue;
 #define CASE_Y(T, LG, NBL) \
     if (a1.lg == LG && nbl == NBL && dtype == (sizeof(T) == 4 ? 0 : 1)) \
-      return run_passB_shared<T, LG, false, 16, NBL, false, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, raw, nullptr, ys);
+      return run_passB_shared<T, LG, false, 16, NBL, false, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, raw, nullptr, ys, skipcnt);
     CASE_Y(float, 11, 6) CASE_Y(float, 12, 6) CASE_Y(float, 11, 8) CASE_Y(float, 12, 8) CASE_Y(double, 11, 8) CASE_Y(double, 12, 8)
 #undef CASE_Y
     return hipErrorInvalidValue;
   }
 #define CALL_S(T, LG, NBL) \
-  (a1.padded ? run_passB_shared<T, LG, true, 16, NBL>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, raw) \
-             : run_passB_shared<T, LG, false, 16, NBL>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, raw))
+  (a1.padded ? run_passB_shared<T, LG, true, 16, NBL>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, raw, nullptr, nullptr, skipcnt) \
+             : run_passB_shared<T, LG, false, 16, NBL>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, raw, nullptr, nullptr, skipcnt))
 #define CASE_S(LG, NBL) \
   if (a1.lg == LG && nbl == NBL) return dtype == 0 ? CALL_S(float, LG, NBL) : CALL_S(double, LG, NBL);
 #define CASE_F32(LG, NBL) \

@@ -239,6 +239,8 @@ struct gpa_plan {
   bool serial_unwrap = false;
   KernelProfiler* kprof = nullptr;   // per-kernel event pairs of the last profiled driver call
   std::string kprof_table;           // "name calls total_ms" lines of that call
+  unsigned long long* d_pbskip = nullptr;   // two words: candidate rows the shared pass B skipped / visited in its last profiled launch
+  bool pbskip_valid = false;                // ... and whether the last shared pass B was such a launch
   // downloads overlapped with the next call (gpa_download_async)
   hipStream_t copy_stream = nullptr;
   hipEvent_t ev_dl_ready = nullptr, ev_dl_done[4] = {nullptr, nullptr, nullptr, nullptr};
