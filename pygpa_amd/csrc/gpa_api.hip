@@ -74,12 +74,18 @@ int upload_real_table(gpa_plan* p, void* dst, const std::vector<double>& v) {
   return GPA_OK;
 }
 
+int plan_reserve(gpa_plan* p, DevBuf& b, size_t bytes, const char* what) {
+  const hipError_t e = b.reserve(bytes, p->stream);
+  if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string(what) + "(" + std::to_string(bytes) + "): " + hipGetErrorString(e));
+  return GPA_OK;
+}
+
+// the single door of the fixed and allocate-once device buffers: the plan owns what it hands out and frees it when it goes
 int dmalloc(gpa_plan* p, void** ptr, size_t bytes) {
-  if (bytes == 0) bytes = 16;
-  hipError_t e = hipMalloc(ptr, bytes);
-  if (e != hipSuccess)
-    return fail(GPA_ERR_HIP, std::string("hipMalloc(") + std::to_string(bytes) + "): " + hipGetErrorString(e));
-  p->ws_bytes += bytes;
+  DevBuf b(&p->ws_bytes);
+  TRY(plan_reserve(p, b, bytes, "hipMalloc"));
+  *ptr = b.ptr;
+  p->owned.push_back(std::move(b));
   return GPA_OK;
 }
 int plan_build(gpa_plan* p) {
@@ -90,23 +96,16 @@ int plan_build(gpa_plan* p) {
   for (auto& e : p->stage_ev) HIP_TRY(hipEventCreate(&e));
   const size_t npx = (size_t)p->n0 * p->n1;
   const int B = p->max_batch;
-  for (int ax = 0; ax < 2; ++ax) {
-    const Axis& a = ax == 0 ? p->ax0 : p->ax1;
-    std::vector<double> t((size_t)2 * a.L);
-    for (int k = 0; k < a.L; ++k) {
-      t[2 * k] = cos(-2.0 * M_PI * k / a.L);
-      t[2 * k + 1] = sin(-2.0 * M_PI * k / a.L);
-    }
-    void** dst = ax == 0 ? &p->tw0 : &p->tw1;
-    TRY(dmalloc(p, dst, (size_t)a.L * p->csz));
-    TRY(upload_real_table(p, *dst, t));
-  }
+  TRY(dmalloc(p, &p->tw0, (size_t)p->ax0.L * p->csz));
+  TRY(upload_twiddles(p, p->tw0, p->ax0.L));
+  TRY(dmalloc(p, &p->tw1, (size_t)p->ax1.L * p->csz));
+  TRY(upload_twiddles(p, p->tw1, p->ax1.L));
   TRY(dmalloc(p, &p->Hx, (size_t)p->ax0.L * p->csz));
   TRY(dmalloc(p, &p->Hy, (size_t)p->ax1.L * p->csz));
   // pass A writes one plane per distinct wx, not per candidate (a 6x6 grid x 3 peaks needs 18 planes, not 108):
   // start with what the non-sweep users need (<= 8 real planes) and grow in ensure_tbuf()
   p->tbuf_planes = B < 4 ? B : 4;
-  TRY(dmalloc(p, &p->Tbuf, (size_t)p->tbuf_planes * npx * p->csz));
+  TRY(plan_reserve(p, p->Tbuf, (size_t)p->tbuf_planes * npx * p->csz, "hipMalloc"));
   // (carrier base tables: one entry per thread of a transform, L / 16)
   TRY(dmalloc(p, &p->tb.cxb, (size_t)B * std::max(p->ax0.L / 16, 256) * p->csz));
   TRY(dmalloc(p, &p->tb.sx, (size_t)B * 16 * p->csz));
@@ -122,8 +121,8 @@ int plan_build(gpa_plan* p) {
   TRY(dmalloc(p, &p->tb.dy, (size_t)B * p->n1 * p->csz));
   TRY(dmalloc(p, (void**)&p->d_kl, (size_t)B * 2 * sizeof(double)));
   TRY(dmalloc(p, (void**)&p->d_kr, (size_t)B * 2 * sizeof(double)));
-  HIP_TRY(hipHostMalloc((void**)&p->h_k, ((size_t)B * 6 + 32) * sizeof(double)));
-  HIP_TRY(hipHostMalloc((void**)&p->h_iters, 8 * sizeof(int)));
+  TRY(plan_reserve(p, p->h_k, ((size_t)B * 6 + 32) * sizeof(double), "hipHostMalloc"));
+  TRY(plan_reserve(p, p->h_iters, 8 * sizeof(int), "hipHostMalloc"));
   TRY(dmalloc(p, &p->d_image, npx * p->rsz));
   TRY(dmalloc(p, &p->d_mean, 16));
   TRY(dmalloc(p, &p->d_tile_mean, 16));
@@ -235,48 +234,23 @@ void gpa_plan_destroy(gpa_plan* p) {
   delete p->worker;
   p->worker = nullptr;
   if (p->stream) hipStreamSynchronize(p->stream);
-  void* bufs[] = {p->tw0, p->tw1, p->Hx, p->Hy, p->Tbuf, p->tb.cxb, p->tb.sx, p->tb.wxw, p->tb.wxr, p->tb.cyb, p->tb.sy, p->tb.wyw, p->tb.wyr, p->tb.planeof, p->d_pw,
-                  p->tb.dx, p->tb.dy, p->d_kl, p->d_kr, p->d_image, p->d_mean, p->d_tile_mean, p->d_scratch,
-                  p->d_lockin, p->d_kidx, p->d_dudx, p->d_dudy, p->d_wnorm, p->d_u, p->d_kmat, p->d_sf, p->d_grad, p->d_grads, p->d_absw, p->d_aux0, p->d_aux1,
-                  p->sh.Gb, p->sh.psi, p->sh.dyc, p->sh.gtab, p->sh.desc, p->sh.order, p->d_taps, p->tw1s,
-                  p->sh.pre, p->sh.rot16, p->d_wys, p->d_shifts, p->d_ystep, p->ys.Yhat, p->ys.strips, p->d_ys_groups, p->d_pbskip};
-  for (void* b : bufs)
-    if (b) hipFree(b);
+  if (p->stream2) hipStreamSynchronize(p->stream2);
+  if (p->copy_stream) hipStreamSynchronize(p->copy_stream);
   unwrap_workspace_destroy(&p->uw);
   unwrap_workspace_destroy(&p->uw2);
   if (p->uwb_images) unwrap_workspace_destroy(&p->uwb);
   if (p->have_uwp) unwrap_workspace_destroy(&p->uwp);
-  if (p->d_wnorm_b) (void)hipFree(p->d_wnorm_b);
-  if (p->h_iters_b) (void)hipHostFree(p->h_iters_b);
-  for (void* b : {p->bT, p->bL, p->bMean, (void*)p->bScratch})
-    if (b) (void)hipFree(b);
-  if (p->stream2) { hipStreamSynchronize(p->stream2); hipStreamDestroy(p->stream2); }
+  if (p->stream2) hipStreamDestroy(p->stream2);
   if (p->ev_fork) hipEventDestroy(p->ev_fork);
   if (p->ev_join) hipEventDestroy(p->ev_join);
   if (p->ev_x) hipEventDestroy(p->ev_x);
-  if (p->d_tsum_part) (void)hipFree(p->d_tsum_part);
-  warp_ws_free(&p->warp);
-  ucell_ws_free(&p->ucell);
   dft_axis_destroy(&p->bx0);
   dft_axis_destroy(&p->bx1);
-  dft_work_free(&p->dftw);
-  for (auto& ax : p->gft)
-    for (auto& g : ax) {
-      if (g.H) (void)hipFree(g.H);
-      if (g.tw) (void)hipFree(g.tw);
-    }
-  if (p->d_pertab) (void)hipFree(p->d_pertab);
-  if (p->d_peakws) (void)hipFree(p->d_peakws);
-  if (p->d_peaksmooth) (void)hipFree(p->d_peaksmooth);
-  if (p->d_iter) (void)hipFree(p->d_iter);
-  if (p->h_iter) (void)hipHostFree(p->h_iter);
-  if (p->h_k) hipHostFree(p->h_k);
-  if (p->h_iters) hipHostFree(p->h_iters);
   if (p->kprof) {
     for (int i = 0; i < p->kprof->npool; ++i) hipEventDestroy(p->kprof->pool[i]);
     delete p->kprof;
   }
-  if (p->copy_stream) { hipStreamSynchronize(p->copy_stream); hipStreamDestroy(p->copy_stream); }
+  if (p->copy_stream) hipStreamDestroy(p->copy_stream);
   if (p->ev_dl_ready) hipEventDestroy(p->ev_dl_ready);
   for (auto e : p->ev_dl_done)
     if (e) hipEventDestroy(e);
@@ -285,7 +259,7 @@ void gpa_plan_destroy(gpa_plan* p) {
   for (auto e : p->stage_ev)
     if (e) hipEventDestroy(e);
   if (p->stream) hipStreamDestroy(p->stream);
-  delete p;
+  delete p;   // the plan's buffers (`owned` and the DevBuf members) free themselves
 }
 
 int gpa_plan_sync(gpa_plan* p) {
@@ -295,7 +269,7 @@ int gpa_plan_sync(gpa_plan* p) {
   if (p->copy_stream) HIP_TRY(hipStreamSynchronize(p->copy_stream));
   return GPA_OK;
 }
-size_t gpa_plan_workspace_bytes(const gpa_plan* p) { return p ? p->ws_bytes : 0; }
+size_t gpa_plan_workspace_bytes(const gpa_plan* p) { return p ? p->ws_bytes + p->uwb_bytes : 0; }
 void* gpa_plan_stream(const gpa_plan* p) { return p ? (void*)p->stream : nullptr; }
 int gpa_plan_fft_len(const gpa_plan* p, int axis) {
   if (!p) return 0;

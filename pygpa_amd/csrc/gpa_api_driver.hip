@@ -67,17 +67,17 @@ static int extract_launch(gpa_plan* p, const void* image, int P, int K, int Bx, 
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[0], p->stream));
   HIP_TRY(launch_mean(p->dtype, image, npx, p->d_scratch, p->d_mean, p->stream));
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[1], p->stream));
-  TRY(run_passA(p, image, p->d_mean, p->Tbuf, Bx, 1));
+  TRY(run_passA(p, image, p->d_mean, p->Tbuf.ptr, Bx, 1));
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[2], p->stream));
   if (o.grads) {
     int32_t* kidx = o.kidx ? o.kidx : p->d_kidx;   // (the stencil reads the winners' indices)
     bool shared = false;
-    TRY(passB_phases(p, P, K, lk, kidx, p->d_sf, &shared));
-    HIP_TRY(launch_phasegrad(p->dtype, p->d_sf, K, kidx, p->n0, p->n1, p->d_kl, p->d_kr, o.grad_mode, o.grads, p->stream,
+    TRY(passB_phases(p, P, K, lk, kidx, p->d_sf.ptr, &shared));
+    HIP_TRY(launch_phasegrad(p->dtype, p->d_sf.ptr, K, kidx, p->n0, p->n1, p->d_kl, p->d_kr, o.grad_mode, o.grads, p->stream,
                              shared ? p->d_ystep : nullptr, P));
   } else {
     // (lock-ins nobody reads but reconstruct_setup may stay raw)
-    TRY(passB_select(p, {p->Tbuf, 1, 0}, P, K, lk, o.kidx, !o.lockins && !o.absw));
+    TRY(passB_select(p, {p->Tbuf.ptr, 1, 0}, P, K, lk, o.kidx, !o.lockins && !o.absw));
   }
   if (o.absw) HIP_TRY(launch_cabs(p->dtype, lk, (size_t)P * npx, o.absw, p->stream));
   const double* ystep = p->lk_raw ? p->d_ystep : nullptr;
@@ -91,7 +91,7 @@ static int extract_launch(gpa_plan* p, const void* image, int P, int K, int Bx, 
                                      unwrap_partials_buffer(&p->uwp, 0), unwrap_partials_buffer(&p->uwp, 1), &nparts,
                                      p->stream, 1, 0, 0, ystep));
     hipError_t ep = unwrap_enqueue_prepared(&p->uwp, p->d_wnorm, nparts, kmax, 1e-9, true, u, p->stream);
-    if (ep == hipSuccess) ep = unwrap_fetch_iters(&p->uwp, p->h_iters, p->stream);
+    if (ep == hipSuccess) ep = unwrap_fetch_iters(&p->uwp, p->h_iters.as<int>(), p->stream);
     if (ep != hipSuccess) return unwrap_fail(ep);
     p->iters_stride = 4;
     p->iters_off = unwrap_iters_slot(&p->uwp);
@@ -115,7 +115,7 @@ static int extract_launch(gpa_plan* p, const void* image, int P, int K, int Bx, 
   void* u1 = (char*)u + npx * p->rsz;
   auto second = [&]() {
     e2 = unwrap_enqueue_prepared(&p->uw2, p->d_wnorm, nparts, kmax, 1e-9, true, u1, p->stream2);
-    if (e2 == hipSuccess) e2 = unwrap_fetch_iters(&p->uw2, &p->h_iters[1], p->stream2);
+    if (e2 == hipSuccess) e2 = unwrap_fetch_iters(&p->uw2, p->h_iters.as<int>() + 1, p->stream2);
   };
   if (threaded) {
     if (!p->worker) p->worker = new EnqueueWorker(p->device);
@@ -126,7 +126,7 @@ static int extract_launch(gpa_plan* p, const void* image, int P, int K, int Bx, 
     HIP_TRY(hipEventRecord(p->ev_fork, p->stream));
     HIP_TRY(hipStreamWaitEvent(p->stream2, p->ev_fork, 0));
   }
-  if (e == hipSuccess) e = unwrap_fetch_iters(&p->uw, &p->h_iters[0], p->stream);
+  if (e == hipSuccess) e = unwrap_fetch_iters(&p->uw, p->h_iters.as<int>(), p->stream);
   if (threaded) p->worker->wait(); else second();
   if (e == hipSuccess) e = e2;
   if (e != hipSuccess) return unwrap_fail(e);
@@ -159,8 +159,9 @@ static int extract_enqueue(gpa_plan* p, const char* what, const void* image, con
 
 // the iteration counts of the last driver call, once its stream has been waited for
 static void read_iters(const gpa_plan* p, int* iters2) {
-  iters2[0] = p->h_iters[p->iters_off];
-  iters2[1] = p->h_iters[p->iters_stride + p->iters_off];
+  const int* h = p->h_iters.as<int>();
+  iters2[0] = h[p->iters_off];
+  iters2[1] = h[p->iters_stride + p->iters_off];
 }
 
 int gpa_last_iters(gpa_plan* p, int* iters2) {
@@ -260,16 +261,10 @@ static int ensure_batch_unwrap(gpa_plan* p, int B) {
     if (!unwrap_set_active(&p->uwb, 2 * B)) return fail(GPA_ERR_STATE, "batched unwrap workspace: bad active count");
     return GPA_OK;
   }
-  const size_t npx = (size_t)p->n0 * p->n1;
   HIP_TRY(hipStreamSynchronize(p->stream));
-  if (p->uwb_images) {
-    unwrap_workspace_destroy(&p->uwb);
-    (void)hipFree(p->d_wnorm_b);
-    (void)hipHostFree(p->h_iters_b);
-    p->uwb_images = 0;
-    p->d_wnorm_b = nullptr;
-    p->h_iters_b = nullptr;
-  }
+  if (p->uwb_images) unwrap_workspace_destroy(&p->uwb);
+  p->uwb_images = 0;
+  p->uwb_bytes = 0;
   size_t bb = 0;
   hipError_t e = unwrap_workspace_create(p->dtype, p->n0, p->n1, p->stream, &p->uwb, &bb, 2 * B);
   if (e != hipSuccess) {
@@ -280,43 +275,29 @@ static int ensure_batch_unwrap(gpa_plan* p, int B) {
     unwrap_workspace_destroy(&p->uwb);
     return fail(GPA_ERR_STATE, "gpa_extract_displacement_field_batch: this image shape has no batched unwrap");
   }
-  e = hipMalloc(&p->d_wnorm_b, (size_t)B * npx * p->rsz);
-  if (e == hipSuccess) e = hipHostMalloc((void**)&p->h_iters_b, (size_t)8 * B * sizeof(int));
+  e = p->d_wnorm_b.reserve((size_t)B * p->n0 * p->n1 * p->rsz, p->stream);
+  if (e == hipSuccess) e = p->h_iters_b.reserve((size_t)8 * B * sizeof(int), p->stream);
   if (e != hipSuccess) {
     unwrap_workspace_destroy(&p->uwb);
-    if (p->d_wnorm_b) (void)hipFree(p->d_wnorm_b);
-    p->d_wnorm_b = nullptr;
     return fail(GPA_ERR_HIP, std::string("batched driver buffers: ") + hipGetErrorString(e));
   }
   p->uwb_images = B;
+  p->uwb_bytes = bb;
   return GPA_OK;
 }
 
 // x-planes (t_img bytes per image), lock-ins (l_img), means and mean scratch of a chunk of images swept in one set of launches
 static int ensure_batch_sweep(gpa_plan* p, int chunk, size_t t_img, size_t l_img) {
-  if ((size_t)chunk * t_img <= p->bT_bytes && (size_t)chunk * l_img <= p->bL_bytes && chunk <= p->b_chunk) return GPA_OK;
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  for (void* b : {p->bT, p->bL, p->bMean, (void*)p->bScratch})
-    if (b) (void)hipFree(b);
-  p->bT = p->bL = p->bMean = nullptr;
-  p->bScratch = nullptr;
-  p->bT_bytes = p->bL_bytes = 0;
-  p->b_chunk = 0;
-  hipError_t ea = hipMalloc(&p->bT, (size_t)chunk * t_img);
-  if (ea == hipSuccess) ea = hipMalloc(&p->bL, (size_t)chunk * l_img);
-  if (ea == hipSuccess) ea = hipMalloc(&p->bMean, (size_t)chunk * 8);
-  if (ea == hipSuccess) ea = hipMalloc((void**)&p->bScratch, (size_t)chunk * 1024 * sizeof(double));
-  if (ea != hipSuccess) return fail(GPA_ERR_HIP, std::string("batched sweep buffers: ") + hipGetErrorString(ea));
-  p->bT_bytes = (size_t)chunk * t_img;
-  p->bL_bytes = (size_t)chunk * l_img;
-  p->b_chunk = chunk;
-  return GPA_OK;
+  TRY(plan_reserve(p, p->bT, (size_t)chunk * t_img, "batched sweep buffers"));
+  TRY(plan_reserve(p, p->bL, (size_t)chunk * l_img, "batched sweep buffers"));
+  TRY(plan_reserve(p, p->bMean, (size_t)chunk * 8, "batched sweep buffers"));
+  return plan_reserve(p, p->bScratch, (size_t)chunk * 1024 * sizeof(double), "batched sweep buffers");
 }
 
 // the iteration counts of the last batched call (2 per image), after waiting for it
 static int read_batch_iters(gpa_plan* p, int B, int* iters_out) {
   HIP_TRY(hipStreamSynchronize(p->stream));
-  for (int j = 0; j < 2 * B; ++j) iters_out[j] = p->h_iters_b[4 * j + unwrap_iters_slot(&p->uwb)];
+  for (int j = 0; j < 2 * B; ++j) iters_out[j] = p->h_iters_b.as<int>()[4 * j + unwrap_iters_slot(&p->uwb)];
   return GPA_OK;
 }
 
@@ -348,17 +329,17 @@ int gpa_extract_displacement_field_batch_dev(gpa_plan* p, const void* images, in
   for (int c0 = 0; c0 < B; c0 += chunk) {
     const int nimg = std::min(chunk, B - c0);
     const void* image = (const char*)images + (size_t)c0 * npx * p->rsz;
-    HIP_TRY(launch_mean(p->dtype, image, npx, p->bScratch, p->bMean, p->stream, nimg));
-    TRY(run_passA(p, image, p->bMean, p->bT, Bx, nimg));
-    TRY(passB_select(p, {p->bT, nimg, Bx}, P, K, p->bL, nullptr, true));   // (the stack's lock-ins are never handed out)
-    HIP_TRY(launch_reconstruct_setup(p->dtype, p->bL, p->d_kmat, P, p->n0, p->n1, mask_border,
-                                     (char*)p->d_wnorm_b + (size_t)c0 * npx * p->rsz,
+    HIP_TRY(launch_mean(p->dtype, image, npx, p->bScratch.as<double>(), p->bMean.ptr, p->stream, nimg));
+    TRY(run_passA(p, image, p->bMean.ptr, p->bT.ptr, Bx, nimg));
+    TRY(passB_select(p, {p->bT.ptr, nimg, Bx}, P, K, p->bL.ptr, nullptr, true));   // (the stack's lock-ins are never handed out)
+    HIP_TRY(launch_reconstruct_setup(p->dtype, p->bL.ptr, p->d_kmat, P, p->n0, p->n1, mask_border,
+                                     p->d_wnorm_b.as<char>() + (size_t)c0 * npx * p->rsz,
                                      unwrap_residual_buffer(&p->uwb, 2 * c0), unwrap_residual_buffer(&p->uwb, 2 * c0 + 1),
                                      unwrap_partials_buffer(&p->uwb, 2 * c0), unwrap_partials_buffer(&p->uwb, 2 * c0 + 1),
                                      &nparts, p->stream, nimg, rstride, pstride, p->lk_raw ? p->d_ystep : nullptr));
   }
-  hipError_t e = unwrap_enqueue_prepared(&p->uwb, p->d_wnorm_b, nparts, kmax, 1e-9, true, u, p->stream);
-  if (e == hipSuccess) e = unwrap_fetch_iters(&p->uwb, p->h_iters_b, p->stream);
+  hipError_t e = unwrap_enqueue_prepared(&p->uwb, p->d_wnorm_b.ptr, nparts, kmax, 1e-9, true, u, p->stream);
+  if (e == hipSuccess) e = unwrap_fetch_iters(&p->uwb, p->h_iters_b.as<int>(), p->stream);
   if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("batched unwrap: ") + hipGetErrorString(e));
   return iters_out ? read_batch_iters(p, B, iters_out) : GPA_OK;
 }

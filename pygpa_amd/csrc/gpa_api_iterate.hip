@@ -5,32 +5,7 @@
 #include "gpa_plan.h"
 
 // the plan's a8 scratch, at least `bytes` (grown with a stream synchronisation; counted in gpa_plan_workspace_bytes)
-static int ensure_iter(gpa_plan* p, size_t bytes) {
-  if (p->iter_bytes >= bytes) return GPA_OK;
-  if (p->d_iter) {
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    HIP_TRY(hipFree(p->d_iter));
-    p->ws_bytes -= p->iter_bytes;
-    p->d_iter = nullptr;
-    p->iter_bytes = 0;
-  }
-  TRY(dmalloc(p, &p->d_iter, bytes));
-  p->iter_bytes = bytes;
-  return GPA_OK;
-}
-
-static int ensure_iter_host(gpa_plan* p, int P) {
-  if (p->h_iter_planes >= (size_t)P) return GPA_OK;
-  if (p->h_iter) {
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    HIP_TRY(hipHostFree(p->h_iter));
-    p->h_iter = nullptr;
-    p->h_iter_planes = 0;
-  }
-  HIP_TRY(hipHostMalloc((void**)&p->h_iter, (size_t)P * 14 * sizeof(double)));
-  p->h_iter_planes = P;
-  return GPA_OK;
-}
+static int ensure_iter(gpa_plan* p, size_t bytes) { return plan_reserve(p, p->d_iter, bytes, "hipMalloc"); }
 
 // the head of the scratch: Huber work of P planes, then their 4-double states and 10-double sums; a multiple of 256 bytes
 static size_t fit_bytes(int P) {
@@ -41,15 +16,15 @@ static size_t fit_bytes(int P) {
 // gpa_fit_plane_dev of P contiguous planes: every round is one launch pair and one readback for all planes that still move.
 // p->d_iter holds at least fit_bytes(P).
 static int fit_planes_run(gpa_plan* p, const void* images, int P, int max_iter, double tol, double* coef, int* iters_out) {
-  TRY(ensure_iter_host(p, P));
+  TRY(plan_reserve(p, p->h_iter, (size_t)P * 14 * sizeof(double), "hipHostMalloc"));
   const int n0 = p->n0, n1 = p->n1;
   const double cx = 0.5 * (n0 - 1), cy = 0.5 * (n1 - 1), sx = 0.5 * n0, sy = 0.5 * n1;
   const size_t stride = huber_batch_stride();
-  double* work = (double*)p->d_iter;
+  double* work = p->d_iter.as<double>();
   double* d_state = work + (size_t)P * stride;
   double* d_sums = d_state + (size_t)4 * P;
-  double* h_state = p->h_iter;
-  double* h_sums = p->h_iter + (size_t)4 * P;
+  double* h_state = p->h_iter.as<double>();
+  double* h_sums = h_state + (size_t)4 * P;
   std::vector<double> c((size_t)3 * P, 0.0);   // every plane starts at the zero plane
   std::vector<int> its((size_t)P, 0);
   std::vector<char> live((size_t)P, 1);
@@ -159,7 +134,7 @@ static int iterate_run(gpa_plan* p, gpa_plan* cp, const void* image, const doubl
                        int iters, int kmax_iter, int kmax, void* prs, void* w, double* corr, double* delta_ks,
                        int* unwrap_iters) {
   const size_t npx = (size_t)p->n0 * p->n1, m = (size_t)cp->n0 * cp->n1;
-  char* base = (char*)cp->d_iter;
+  char* base = cp->d_iter.as<char>();
   void* amax = base + fit_bytes(P);
   char* psi = base + iterate_planes_at(P);
   char* weight = psi + (size_t)P * m * p->rsz;
@@ -183,9 +158,9 @@ static int iterate_run(gpa_plan* p, gpa_plan* cp, const void* image, const doubl
   for (int pass = 0; pass <= iters; ++pass) {
     const bool last = pass == iters;
     for (int i = 0; i < 2 * P; ++i) ks[i] = kvecs[i] + corr[i];
-    TRY(gpa_lockin_batch_dev(p, image, ks.data(), P, sigma, p->d_sf));
+    TRY(gpa_lockin_batch_dev(p, image, ks.data(), P, sigma, p->d_sf.ptr));
     TRY(mark(0));
-    TRY(gpa_lockin_polar_crop_dev(p, p->d_sf, P, edge, psi, w, weight, amax));
+    TRY(gpa_lockin_polar_crop_dev(p, p->d_sf.ptr, P, edge, psi, w, weight, amax));
     if (cp != p) {
       HIP_TRY(hipEventRecord(p->ev_x, p->stream));
       HIP_TRY(hipStreamWaitEvent(cp->stream, p->ev_x, 0));
@@ -232,7 +207,7 @@ int gpa_iterate_gpa(gpa_plan* p, gpa_plan* crop, const void* image, const double
   const size_t npx = (size_t)p->n0 * p->n1, m = (size_t)cp->n0 * cp->n1, planes = (size_t)P * m * p->rsz;
   // the scratch's last two plane sets stage prs and w
   TRY(ensure_iter(cp, iterate_planes_at(P) + 4 * planes));
-  char* d_prs = (char*)cp->d_iter + iterate_planes_at(P) + 2 * planes;
+  char* d_prs = cp->d_iter.as<char>() + iterate_planes_at(P) + 2 * planes;
   char* d_w = d_prs + planes;
   HIP_TRY(hipMemcpyAsync(p->d_image, image, npx * p->rsz, hipMemcpyHostToDevice, p->stream));
   TRY(iterate_run(p, cp, p->d_image, kvecs, P, sigma, edge, iters, kmax_iter, kmax, d_prs, d_w, corr, delta_ks, unwrap_iters));

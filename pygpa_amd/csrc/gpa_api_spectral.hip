@@ -10,7 +10,6 @@ int dft_axes(gpa_plan* p) {
     force = !strcmp(v, "chirpz2") ? DFT_BIG : !strcmp(v, "chirpz") ? DFT_BLUE : 0;
   }
   size_t b = 0;
-  p->dftw.counted = &p->ws_bytes;
   hipError_t e = dft_axis_create(p->dtype, p->n0, p->stream, &p->bx0, &b, force);
   if (e == hipSuccess) e = dft_axis_create(p->dtype, p->n1, p->stream, &p->bx1, &b, force);
   if (e != hipSuccess) {
@@ -36,11 +35,11 @@ int per_dft_staged(gpa_plan* p, const void* d_image, void* abs_out) {
   HIP_TRY(per_borders(p->dtype, d_image, p->n0, p->n1, d0, d1, p->stream));
   // |P^| is symmetric under (q, r) -> (-q, -r): for abs_out half of u_hat is enough (power-of-two rows; NO_DFT_HALF: tests)
   const size_t hp = abs_out && !opt_set(OPT_NO_DFT_HALF) ? dft2_half_pitch(p->bx1) : 0;
-  if (hp) HIP_TRY(dft2_forward_real_half(p->dtype, p->bx0, p->bx1, d_image, p->Tbuf, &p->dftw, p->stream));
-  else HIP_TRY(dft2_forward_real(p->dtype, p->bx0, p->bx1, d_image, p->Tbuf, &p->dftw, p->stream));
+  if (hp) HIP_TRY(dft2_forward_real_half(p->dtype, p->bx0, p->bx1, d_image, p->Tbuf.ptr, &p->dftw, p->stream));
+  else HIP_TRY(dft2_forward_real(p->dtype, p->bx0, p->bx1, d_image, p->Tbuf.ptr, &p->dftw, p->stream));
   HIP_TRY(dft_rows_inplace(p->dtype, p->bx1, 1, d0, &p->dftw, p->stream));
   HIP_TRY(dft_rows_inplace(p->dtype, p->bx0, 1, d1, &p->dftw, p->stream));
-  HIP_TRY(per_combine(p->dtype, p->Tbuf, d0, d1, p->n0, p->n1, p->d_pertab, abs_out != nullptr,
+  HIP_TRY(per_combine(p->dtype, p->Tbuf.ptr, d0, d1, p->n0, p->n1, p->d_pertab, abs_out != nullptr,
                       abs_out ? abs_out : p->d_lockin, p->stream, hp));
   return GPA_OK;
 }
@@ -76,8 +75,8 @@ int gpa_per(gpa_plan* p, const void* image, int inverse_dft, void* p_out, void* 
   if (!inverse_dft) {
     HIP_TRY(hipMemcpyAsync(p_out, p->d_lockin, npx * p->csz, hipMemcpyDeviceToHost, p->stream));
     if (s_out) {
-      HIP_TRY(per_smooth_hat(p->dtype, p->Tbuf, p->d_lockin, npx, p->stream));
-      HIP_TRY(hipMemcpyAsync(s_out, p->Tbuf, npx * p->csz, hipMemcpyDeviceToHost, p->stream));
+      HIP_TRY(per_smooth_hat(p->dtype, p->Tbuf.ptr, p->d_lockin, npx, p->stream));
+      HIP_TRY(hipMemcpyAsync(s_out, p->Tbuf.ptr, npx * p->csz, hipMemcpyDeviceToHost, p->stream));
     }
   } else {
     HIP_TRY(per_components(p->dtype, p->bx0, p->bx1, p->d_lockin, p->d_image, p->d_wnorm, p->d_dudx, &p->dftw, p->stream));
@@ -109,23 +108,16 @@ static int gauss_tables(gpa_plan* p, int axis, double sigma, int lg, const std::
     HIP_TRY(hipStreamSynchronize(p->stream));   // an earlier call may still read the tables being replaced
     slot->sigma = -1.0;
     const size_t L = (size_t)1 << lg;
-    if (slot->cap_lg < lg) {
-      if (slot->H) { (void)hipFree(slot->H); p->ws_bytes -= ((size_t)1 << slot->cap_lg) * p->rsz; }
-      if (slot->tw) { (void)hipFree(slot->tw); p->ws_bytes -= ((size_t)1 << slot->cap_lg) * p->csz; }
-      slot->H = slot->tw = nullptr;
-      slot->cap_lg = 0;
-      TRY(dmalloc(p, &slot->H, L * p->rsz));
-      TRY(dmalloc(p, &slot->tw, L * p->csz));
-      slot->cap_lg = lg;
-    }
-    TRY(upload_real_table(p, slot->H, gaussfft_table(lg, w)));
-    TRY(upload_twiddles(p, slot->tw, (int)L));
+    TRY(plan_reserve(p, slot->H, L * p->rsz, "hipMalloc"));
+    TRY(plan_reserve(p, slot->tw, L * p->csz, "hipMalloc"));
+    TRY(upload_real_table(p, slot->H.ptr, gaussfft_table(lg, w)));
+    TRY(upload_twiddles(p, slot->tw.ptr, (int)L));
     slot->sigma = sigma;
     slot->lg = lg;
   }
   slot->stamp = ++p->gft_clock;
-  *H = slot->H;
-  *tw = slot->tw;
+  *H = slot->H.ptr;
+  *tw = slot->tw.ptr;
   return GPA_OK;
 }
 
@@ -264,11 +256,11 @@ int gpa_gaussian_deconvolve_dev(gpa_plan* p, const void* d_data, int dr, double 
   double* d_gy = reinterpret_cast<double*>(p->d_aux1);
   HIP_TRY(hipMemcpyAsync(d_gx, gx.data(), (size_t)n0 * sizeof(double), hipMemcpyHostToDevice, st));
   HIP_TRY(hipMemcpyAsync(d_gy, gy.data(), (size_t)n1 * sizeof(double), hipMemcpyHostToDevice, st));
-  HIP_TRY(launch_deconv_pack(p->dtype, d_data, m0, m1, pad, p->Tbuf, st));
-  HIP_TRY(dft2_inplace(p->dtype, p->bx0, p->bx1, p->Tbuf, &p->dftw, st));
-  HIP_TRY(launch_deconv_filter(p->dtype, p->Tbuf, n0, n1, d_gx, d_gy, balance, st));
-  HIP_TRY(dft2_inplace(p->dtype, p->bx0, p->bx1, p->Tbuf, &p->dftw, st));
-  HIP_TRY(launch_deconv_unpack(p->dtype, p->Tbuf, m0, m1, pad, d_out, st));
+  HIP_TRY(launch_deconv_pack(p->dtype, d_data, m0, m1, pad, p->Tbuf.ptr, st));
+  HIP_TRY(dft2_inplace(p->dtype, p->bx0, p->bx1, p->Tbuf.ptr, &p->dftw, st));
+  HIP_TRY(launch_deconv_filter(p->dtype, p->Tbuf.ptr, n0, n1, d_gx, d_gy, balance, st));
+  HIP_TRY(dft2_inplace(p->dtype, p->bx0, p->bx1, p->Tbuf.ptr, &p->dftw, st));
+  HIP_TRY(launch_deconv_unpack(p->dtype, p->Tbuf.ptr, m0, m1, pad, d_out, st));
   HIP_TRY(hipStreamSynchronize(st));   // gx / gy are pageable host vectors
   if (p->profiling) collect_kernel_profile(p);
   return GPA_OK;
@@ -321,17 +313,14 @@ int gpa_phasegradient2J(gpa_plan* p, const double* kvecs, int P, const void* gra
   HIP_TRY(hipSetDevice(p->device));
   const size_t npx = (size_t)p->n0 * p->n1;
   TRY(ensure_tbuf(p, (P + 1) / 2));
-  void* d_J = nullptr;
-  HIP_TRY(hipMalloc(&d_J, 4 * npx * p->rsz));
-  int rc = GPA_OK;
-  hipError_t e = hipMemcpyAsync(p->d_lockin, grads, (size_t)P * npx * 2 * p->rsz, hipMemcpyHostToDevice, p->stream);
-  if (e == hipSuccess) e = hipMemcpyAsync(p->Tbuf, weights, (size_t)P * npx * p->rsz, hipMemcpyHostToDevice, p->stream);
-  if (e == hipSuccess) rc = gpa_phasegradient2J_dev(p, kvecs, P, p->d_lockin, p->Tbuf, nmperpixel, dks, d_J);
-  if (e == hipSuccess && rc == GPA_OK) e = hipMemcpyAsync(J, d_J, 4 * npx * p->rsz, hipMemcpyDeviceToHost, p->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  hipFree(d_J);
-  if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_phasegradient2J: ") + hipGetErrorString(e));
-  return rc;
+  DevBuf d_J;   // a temporary of this call
+  HIP_TRY(d_J.reserve(4 * npx * p->rsz, p->stream));
+  HIP_TRY(hipMemcpyAsync(p->d_lockin, grads, (size_t)P * npx * 2 * p->rsz, hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipMemcpyAsync(p->Tbuf.ptr, weights, (size_t)P * npx * p->rsz, hipMemcpyHostToDevice, p->stream));
+  TRY(gpa_phasegradient2J_dev(p, kvecs, P, p->d_lockin, p->Tbuf.ptr, nmperpixel, dks, d_J.ptr));
+  HIP_TRY(hipMemcpyAsync(J, d_J.ptr, 4 * npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return GPA_OK;
 }
 
 int gpa_props_from_jac_dev(int device, int dtype, size_t npx, const void* jac, int add_identity, double refangle,
@@ -353,17 +342,13 @@ int gpa_props_from_jac(int device, int dtype, size_t npx, const void* jac, int a
   if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(GPA_ERR_NODEV, "gpa_props_from_jac: no HIP device");
   HIP_TRY(hipSetDevice(device));
   const size_t bytes = 4 * npx * (dtype == GPA_F32 ? 4 : 8);
-  void *d_j = nullptr, *d_p = nullptr;
-  HIP_TRY(hipMalloc(&d_j, bytes));
-  hipError_t e = hipMalloc(&d_p, bytes);
-  int rc = GPA_OK;
-  if (e == hipSuccess) e = hipMemcpy(d_j, jac, bytes, hipMemcpyHostToDevice);
-  if (e == hipSuccess) rc = gpa_props_from_jac_dev(device, dtype, npx, d_j, add_identity, refangle, refscale, diff, d_p, nullptr);
-  if (e == hipSuccess && rc == GPA_OK) e = hipMemcpy(props, d_p, bytes, hipMemcpyDeviceToHost);
-  hipFree(d_j);
-  hipFree(d_p);
-  if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_props_from_jac: ") + hipGetErrorString(e));
-  return rc;
+  DevBuf d_j, d_p;   // temporaries of this call
+  HIP_TRY(d_j.reserve(bytes, nullptr));
+  HIP_TRY(d_p.reserve(bytes, nullptr));
+  HIP_TRY(hipMemcpy(d_j.ptr, jac, bytes, hipMemcpyHostToDevice));
+  TRY(gpa_props_from_jac_dev(device, dtype, npx, d_j.ptr, add_identity, refangle, refscale, diff, d_p.ptr, nullptr));
+  HIP_TRY(hipMemcpy(props, d_p.ptr, bytes, hipMemcpyDeviceToHost));
+  return GPA_OK;
 }
 
 // ---- f-4 -------------------------------------------------------------------------

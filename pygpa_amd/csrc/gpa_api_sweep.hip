@@ -11,8 +11,8 @@ int gpa_lockin_batch_dev(gpa_plan* p, const void* image, const double* kvecs, in
   int Bx = 0;
   TRY(stage_kvectors(p, kvecs, kvecs, B, &Bx));
   TRY(ensure_tbuf(p, Bx));
-  TRY(run_passA(p, image, nullptr, p->Tbuf, Bx, 1));
-  HIP_TRY(launch_passB(p->dtype, p->ax1, p->n0, p->Tbuf, p->Hy, p->tw1, p->tb, B, 1, false, out, nullptr,
+  TRY(run_passA(p, image, nullptr, p->Tbuf.ptr, Bx, 1));
+  HIP_TRY(launch_passB(p->dtype, p->ax1, p->n0, p->Tbuf.ptr, p->Hy, p->tw1, p->tb, B, 1, false, out, nullptr,
                        p->stream));
   return GPA_OK;
 }
@@ -25,8 +25,8 @@ int gpa_lockin_batch(gpa_plan* p, const void* image, const double* kvecs, int B,
   HIP_TRY(hipMemcpyAsync(p->d_image, image, npx * p->rsz, hipMemcpyHostToDevice, p->stream));
   // pass B reads Tbuf, so the B lock-ins land in the plan's grown-on-demand scratch
   TRY(ensure_sf(p, (size_t)B * npx * p->csz));
-  TRY(gpa_lockin_batch_dev(p, p->d_image, kvecs, B, sigma, p->d_sf));
-  HIP_TRY(hipMemcpyAsync(out, p->d_sf, (size_t)B * npx * p->csz, hipMemcpyDeviceToHost, p->stream));
+  TRY(gpa_lockin_batch_dev(p, p->d_image, kvecs, B, sigma, p->d_sf.ptr));
+  HIP_TRY(hipMemcpyAsync(out, p->d_sf.ptr, (size_t)B * npx * p->csz, hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   return GPA_OK;
 }
@@ -116,8 +116,8 @@ int passB_select(gpa_plan* p, const XPlanes& xp, int P, int K, void* lockin, int
   }
   const size_t npx = (size_t)p->n0 * p->n1, cnt = (size_t)ksplit * P * npx;
   TRY(ensure_sf(p, cnt * (p->csz + sizeof(int32_t))));
-  void* part = p->d_sf;
-  int32_t* pidx = reinterpret_cast<int32_t*>((char*)p->d_sf + cnt * p->csz);
+  void* part = p->d_sf.ptr;
+  int32_t* pidx = reinterpret_cast<int32_t*>((char*)p->d_sf.ptr + cnt * p->csz);
   HIP_TRY(launch_passB_split(p->dtype, p->ax1, p->n0, xp.T, p->Hy, p->tw1, p->tb, P, K, ksplit, part, pidx, lockin, kidx,
                              p->stream));
   return GPA_OK;
@@ -136,7 +136,7 @@ int passB_phases(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, void* p
     p->ys_use = ys;
     if (p->sh_use && p->sh_one_kref) {
       const PassBYspec yb = {p->ys.strips, p->d_shifts};
-      const hipError_t e = launch_passB_shared_phases(p->dtype, p->ax1s, p->n0, p->Tbuf, p->ax1s.L == p->ax1.L ? p->tw1 : p->tw1s,
+      const hipError_t e = launch_passB_shared_phases(p->dtype, p->ax1s, p->n0, p->Tbuf.ptr, p->ax1s.L == p->ax1.L ? p->tw1 : p->tw1s,
                                                       p->tb, p->sh, p->sh_E, p->sh_Epad, P, K, lockin, kidx, psi, p->stream, 0,
                                                       p->sh_nbl, ys ? &yb : nullptr);
       if (e == hipSuccess) {
@@ -148,7 +148,7 @@ int passB_phases(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, void* p
   }
   // (the per-candidate kernel reads spatial x-planes)
   if (ys) return fail(GPA_ERR_STATE, "pass B (phases): the staged sweep took the y-spectral pass A");
-  HIP_TRY(launch_passB_ext(p->dtype, p->ax1, p->n0, p->Tbuf, p->Hy, p->tw1, p->tb, K, 3, lockin, kidx, nullptr, psi, p->stream, P));
+  HIP_TRY(launch_passB_ext(p->dtype, p->ax1, p->n0, p->Tbuf.ptr, p->Hy, p->tw1, p->tb, K, 3, lockin, kidx, nullptr, psi, p->stream, P));
   return GPA_OK;
 }
 
@@ -182,9 +182,9 @@ int sweep_peaks_dev(gpa_plan* p, const void* image, const void* mean, const doub
   int Bx = 0;
   TRY(stage_sweep(p, krefs, P, klists, K, sigma, &Bx, SWEEP_PASSB_SELECT));
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[1], p->stream));
-  TRY(run_passA(p, image, mean, p->Tbuf, Bx, 1));
+  TRY(run_passA(p, image, mean, p->Tbuf.ptr, Bx, 1));
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[2], p->stream));
-  TRY(passB_select(p, {p->Tbuf, 1, 0}, P, K, lockin, kidx, raw));
+  TRY(passB_select(p, {p->Tbuf.ptr, 1, 0}, P, K, lockin, kidx, raw));
   if (p->profiling) HIP_TRY(hipEventRecord(p->stage_ev[3], p->stream));
   return GPA_OK;
 }
@@ -195,8 +195,8 @@ static int sweep_one_peak(gpa_plan* p, const void* image, const double* kref, co
   if (K > p->max_batch) return fail(GPA_ERR_STATE, "gpa_sweep: K exceeds the plan's max_batch");
   int Bx = 0;
   TRY(stage_sweep(p, kref, 1, klist, K, sigma, &Bx));
-  TRY(run_passA(p, image, nullptr, p->Tbuf, Bx, 1));
-  HIP_TRY(launch_passB_ext(p->dtype, p->ax1, p->n0, p->Tbuf, p->Hy, p->tw1, p->tb, K, mode, lockin, kidx, d_gate, d_psi,
+  TRY(run_passA(p, image, nullptr, p->Tbuf.ptr, Bx, 1));
+  HIP_TRY(launch_passB_ext(p->dtype, p->ax1, p->n0, p->Tbuf.ptr, p->Hy, p->tw1, p->tb, K, mode, lockin, kidx, d_gate, d_psi,
                            p->stream));
   return GPA_OK;
 }
@@ -218,13 +218,13 @@ int gpa_sweep_grad_dev(gpa_plan* p, const void* image, const double* kref, const
   int32_t* ki = kidx ? kidx : p->d_kidx;
   int Bx = 0;
   TRY(stage_sweep(p, kref, 1, klist, K, sigma, &Bx, SWEEP_PASSB_PHASES));
-  TRY(run_passA(p, image, nullptr, p->Tbuf, Bx, 1));
+  TRY(run_passA(p, image, nullptr, p->Tbuf.ptr, Bx, 1));
   // rows the shared-forward pass B takes (2048- / 4096- / f32 8192-point classes, lists with runs on their x-planes): one
   // forward transform per x-plane row instead of one per candidate, the phases written by that kernel (round 6; NO_SHARED or
   // NO_SHARED_PHASES keep the per-candidate kernel: the same gradient up to rounding, tests/test_gpu_shared_passb.py)
   bool shared = false;
-  TRY(passB_phases(p, 1, K, lockin, ki, p->d_sf, &shared));
-  HIP_TRY(launch_phasegrad(p->dtype, p->d_sf, K, ki, p->n0, p->n1, p->d_kl, p->d_kr, grad_mode, grad, p->stream,
+  TRY(passB_phases(p, 1, K, lockin, ki, p->d_sf.ptr, &shared));
+  HIP_TRY(launch_phasegrad(p->dtype, p->d_sf.ptr, K, ki, p->n0, p->n1, p->d_kl, p->d_kr, grad_mode, grad, p->stream,
                            shared ? p->d_ystep : nullptr));
   if (top && p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
   return GPA_OK;
@@ -250,8 +250,8 @@ static int sweep_host(gpa_plan* p, const void* image, const double* kref, const 
   if (grad && !p->d_grad) TRY(dmalloc(p, &p->d_grad, 2 * npx * p->rsz));
   if (gate) {
     TRY(ensure_sf(p, (size_t)K * K));
-    HIP_TRY(hipMemcpyAsync(p->d_sf, gate, (size_t)K * K, hipMemcpyHostToDevice, p->stream));
-    TRY(sweep_one_peak(p, p->d_image, kref, klist, K, sigma, 2, p->d_lockin, p->d_kidx, (const uint8_t*)p->d_sf, nullptr));
+    HIP_TRY(hipMemcpyAsync(p->d_sf.ptr, gate, (size_t)K * K, hipMemcpyHostToDevice, p->stream));
+    TRY(sweep_one_peak(p, p->d_image, kref, klist, K, sigma, 2, p->d_lockin, p->d_kidx, (const uint8_t*)p->d_sf.ptr, nullptr));
   } else if (grad) {
     TRY(gpa_sweep_grad_dev(p, p->d_image, kref, klist, K, sigma, grad_mode, p->d_lockin, p->d_kidx, p->d_grad));
   } else {

@@ -353,17 +353,13 @@ int shared_prepare(gpa_plan* p, int P, int K) {
     p->sh_nbl = EEs;
   }
   const size_t gb = (size_t)B * p->ax1s.L * p->rsz, ps = (size_t)B * p->sh_Epad * p->csz;
-  if (gb > p->sh_gb_bytes) {
-    if (p->sh.Gb) { (void)hipFree(p->sh.Gb); p->ws_bytes -= p->sh_gb_bytes; p->sh.Gb = nullptr; p->sh_gb_bytes = 0; }
-    TRY(dmalloc(p, &p->sh.Gb, gb));
-    p->sh_gb_bytes = gb;
-  }
-  if (ps > p->sh_psi_bytes) {
-    if (p->sh.psi) { (void)hipFree(p->sh.psi); (void)hipFree(p->sh.pre); p->ws_bytes -= 2 * p->sh_psi_bytes; p->sh.psi = p->sh.pre = nullptr; p->sh_psi_bytes = 0; }
-    TRY(dmalloc(p, &p->sh.psi, ps));
-    TRY(dmalloc(p, &p->sh.pre, ps));
-    p->sh_psi_bytes = ps;
-  }
+  p->sh.Gb = p->sh.psi = p->sh.pre = nullptr;   // (views of the three buffers: set again once all three stand)
+  TRY(plan_reserve(p, p->sh_Gb, gb, "hipMalloc"));
+  TRY(plan_reserve(p, p->sh_psi, ps, "hipMalloc"));
+  TRY(plan_reserve(p, p->sh_pre, ps, "hipMalloc"));
+  p->sh.Gb = p->sh_Gb.ptr;
+  p->sh.psi = p->sh_psi.ptr;
+  p->sh.pre = p->sh_pre.ptr;
   if (!p->sh.rot16) TRY(dmalloc(p, &p->sh.rot16, (size_t)p->max_peaks * 16 * p->csz));
   if (!p->d_wys) TRY(dmalloc(p, (void**)&p->d_wys, (size_t)p->max_batch * sizeof(double)));
   if (!p->d_shifts) TRY(dmalloc(p, (void**)&p->d_shifts, (size_t)p->max_peaks * sizeof(int)));
@@ -446,10 +442,10 @@ int stage_kvectors(gpa_plan* p, const double* kl, const double* kr_per_b, int B,
   HIP_TRY(hipStreamSynchronize(p->stream));
   p->staged_kl.assign(kl, kl + 2 * (size_t)B);
   p->staged_kr.assign(kr_per_b, kr_per_b + 2 * (size_t)B);
-  double* h_kl = p->h_k;
-  double* h_kr = p->h_k + 2 * (size_t)B;
-  double* h_pw = p->h_k + 4 * (size_t)B;
-  int* h_po = reinterpret_cast<int*>(p->h_k + 5 * (size_t)B);
+  double* h_kl = p->h_k.as<double>();
+  double* h_kr = h_kl + 2 * (size_t)B;
+  double* h_pw = h_kl + 4 * (size_t)B;
+  int* h_po = reinterpret_cast<int*>(h_kl + 5 * (size_t)B);
   memcpy(h_kl, kl, (size_t)B * 2 * sizeof(double));
   memcpy(h_kr, kr_per_b, (size_t)B * 2 * sizeof(double));
   int Bx = 0;
@@ -477,13 +473,8 @@ int stage_kvectors(gpa_plan* p, const double* kl, const double* kr_per_b, int B,
 // room for `planes` x-planes in Tbuf
 int ensure_tbuf(gpa_plan* p, int planes) {
   if (planes <= p->tbuf_planes) return GPA_OK;
-  const size_t npx = (size_t)p->n0 * p->n1;
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  HIP_TRY(hipFree(p->Tbuf));
-  p->ws_bytes -= (size_t)p->tbuf_planes * npx * p->csz;
-  p->Tbuf = nullptr;
   p->tbuf_planes = 0;
-  TRY(dmalloc(p, &p->Tbuf, (size_t)planes * npx * p->csz));
+  TRY(plan_reserve(p, p->Tbuf, (size_t)planes * p->n0 * p->n1 * p->csz, "hipMalloc"));
   p->tbuf_planes = planes;
   return GPA_OK;
 }
@@ -491,35 +482,16 @@ int ensure_tbuf(gpa_plan* p, int planes) {
 // Yhat and the end strips of the y-spectral sweep for nimg images of Bx planes
 int ensure_yspec(gpa_plan* p, int nimg, int Bx) {
   const size_t yb = (size_t)nimg * p->n0 * p->n1 * p->csz, sb = (size_t)nimg * Bx * p->n0 * 2 * p->sh_Epad * p->csz;
-  if (yb > p->ys_yhat_bytes) {
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (p->ys.Yhat) { HIP_TRY(hipFree(p->ys.Yhat)); p->ws_bytes -= p->ys_yhat_bytes; p->ys.Yhat = nullptr; p->ys_yhat_bytes = 0; }
-    TRY(dmalloc(p, &p->ys.Yhat, yb));
-    p->ys_yhat_bytes = yb;
-  }
-  if (sb > p->ys_strips_bytes) {
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (p->ys.strips) { HIP_TRY(hipFree(p->ys.strips)); p->ws_bytes -= p->ys_strips_bytes; p->ys.strips = nullptr; p->ys_strips_bytes = 0; }
-    TRY(dmalloc(p, &p->ys.strips, sb));
-    p->ys_strips_bytes = sb;
-  }
+  p->ys.Yhat = p->ys.strips = nullptr;
+  TRY(plan_reserve(p, p->ys_Yhat, yb, "hipMalloc"));
+  TRY(plan_reserve(p, p->ys_strips, sb, "hipMalloc"));
+  p->ys.Yhat = p->ys_Yhat.ptr;
+  p->ys.strips = p->ys_strips.ptr;
   return GPA_OK;
 }
 
 // scratch of at least `bytes` in p->d_sf (per-candidate phases of the a4 path, gate table of wfr4, batched lock-ins)
-int ensure_sf(gpa_plan* p, size_t bytes) {
-  if (p->sf_bytes >= bytes) return GPA_OK;
-  if (p->d_sf) {
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    HIP_TRY(hipFree(p->d_sf));
-    p->ws_bytes -= p->sf_bytes;
-    p->d_sf = nullptr;
-    p->sf_bytes = 0;
-  }
-  TRY(dmalloc(p, &p->d_sf, bytes));
-  p->sf_bytes = bytes;
-  return GPA_OK;
-}
+int ensure_sf(gpa_plan* p, size_t bytes) { return plan_reserve(p, p->d_sf, bytes, "hipMalloc"); }
 
 // 2 pi kvecs for the per-pixel solves, re-staged only when the peaks change
 int stage_kmat(gpa_plan* p, const double* kvecs, int P) {
@@ -528,7 +500,7 @@ int stage_kmat(gpa_plan* p, const double* kvecs, int P) {
   if (km == p->staged_kmat) return GPA_OK;
   HIP_TRY(hipStreamSynchronize(p->stream));
   p->staged_kmat = km;
-  double* h = p->h_k + 6 * (size_t)p->max_batch;
+  double* h = p->h_k.as<double>() + 6 * (size_t)p->max_batch;
   memcpy(h, km.data(), km.size() * sizeof(double));
   HIP_TRY(hipMemcpyAsync(p->d_kmat, h, km.size() * sizeof(double), hipMemcpyHostToDevice, p->stream));
   return GPA_OK;

@@ -43,12 +43,12 @@ int tile_gradients_impl(gpa_plan* p, const void* image, size_t image_pitch, int 
   if (!mean_on_device && !(mean == p->tile_mean)) {   // tiles of one image share the mean: staged once (d_tile_mean is
     HIP_TRY(hipStreamSynchronize(st));                // not d_mean, which the fused driver recomputes per call)
     if (p->dtype == GPA_F32) {
-      *reinterpret_cast<float*>(p->h_k) = (float)mean;
+      *p->h_k.as<float>() = (float)mean;
     } else {
-      p->h_k[0] = mean;
+      *p->h_k.as<double>() = mean;
     }
     // h_k is pinned and also stages k-vectors: the copy must have left it before stage_kvectors rewrites it
-    HIP_TRY(hipMemcpyAsync(p->d_tile_mean, p->h_k, rsz, hipMemcpyHostToDevice, st));
+    HIP_TRY(hipMemcpyAsync(p->d_tile_mean, p->h_k.ptr, rsz, hipMemcpyHostToDevice, st));
     HIP_TRY(hipStreamSynchronize(st));
     p->tile_mean = mean;
   }
@@ -116,15 +116,9 @@ int gpa_tile_sums_dev(gpa_plan* p, const void* wins, size_t win_stride, size_t w
     return fail(GPA_ERR_ARG, "gpa_tile_sums_dev: bad argument");
   HIP_TRY(hipSetDevice(p->device));
   const size_t need = (size_t)ntiles * tile_sums_bands(max_rows);
-  if (need > p->tsum_cap) {
-    HIP_TRY(hipStreamSynchronize(p->stream));
-    if (p->d_tsum_part) { (void)hipFree(p->d_tsum_part); p->ws_bytes -= p->tsum_cap * sizeof(double); }
-    p->d_tsum_part = nullptr;
-    p->tsum_cap = 0;
-    TRY(dmalloc(p, (void**)&p->d_tsum_part, need * sizeof(double)));
-    p->tsum_cap = need;
-  }
-  HIP_TRY(launch_tile_sums(p->dtype, wins, win_stride, win_pitch, rects_dev, ntiles, max_rows, p->d_tsum_part, sum_dev, p->stream));
+  TRY(plan_reserve(p, p->d_tsum_part, need * sizeof(double), "hipMalloc"));
+  HIP_TRY(launch_tile_sums(p->dtype, wins, win_stride, win_pitch, rects_dev, ntiles, max_rows, p->d_tsum_part.as<double>(), sum_dev,
+                           p->stream));
   return GPA_OK;
 }
 

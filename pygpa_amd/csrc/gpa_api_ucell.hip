@@ -35,7 +35,6 @@ int gpa_unit_cell_average_batch_dev(gpa_plan* p, const void* images_dev, int B, 
   UcellGeom g;
   TRY(check_geom(p, geom, "gpa_unit_cell_average", &g));
   HIP_TRY(hipSetDevice(p->device));
-  p->ucell.counted = &p->ws_bytes;
   ProfInstall prof(p);
   const hipError_t e = ucell_average(p->dtype, images_dev, B, u_dev, p->n0, p->n1, g, res_dev, weights_dev, p->stream, &p->ucell);
   if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_unit_cell_average: ") + hipGetErrorString(e));
@@ -56,18 +55,13 @@ int gpa_unit_cell_average(gpa_plan* p, const void* image, const void* u, const g
   const size_t npx = (size_t)p->n0 * p->n1, ncell = (size_t)g.rs0 * g.rs1;
   HIP_TRY(hipMemcpyAsync(p->d_image, image, npx * p->rsz, hipMemcpyHostToDevice, p->stream));
   if (u) HIP_TRY(hipMemcpyAsync(p->d_u, u, 2 * npx * p->rsz, hipMemcpyHostToDevice, p->stream));
-  p->ucell.counted = &p->ws_bytes;
-  void* stage = nullptr;
-  HIP_TRY(ucell_stage(&p->ucell, 2 * ncell * sizeof(double), p->stream, &stage));
-  double* d_out = (double*)stage;
-  int rc = gpa_unit_cell_average_dev(p, p->d_image, u ? p->d_u : nullptr, geom, d_out, weights ? d_out + ncell : nullptr);
-  hipError_t e = hipSuccess;
-  if (rc == GPA_OK) e = hipMemcpyAsync(res, d_out, ncell * sizeof(double), hipMemcpyDeviceToHost, p->stream);
-  if (rc == GPA_OK && e == hipSuccess && weights)
-    e = hipMemcpyAsync(weights, d_out + ncell, ncell * sizeof(double), hipMemcpyDeviceToHost, p->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_unit_cell_average: ") + hipGetErrorString(e));
-  return rc;
+  HIP_TRY(p->ucell.stage.reserve(2 * ncell * sizeof(double), p->stream));
+  double* d_out = p->ucell.stage.as<double>();
+  TRY(gpa_unit_cell_average_dev(p, p->d_image, u ? p->d_u : nullptr, geom, d_out, weights ? d_out + ncell : nullptr));
+  HIP_TRY(hipMemcpyAsync(res, d_out, ncell * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  if (weights) HIP_TRY(hipMemcpyAsync(weights, d_out + ncell, ncell * sizeof(double), hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return GPA_OK;
 }
 
 int gpa_expand_unitcell_dev(gpa_plan* p, const double* cell_dev, const gpa_ucell_geom* geom, double z2, const void* u_dev,
@@ -77,7 +71,6 @@ int gpa_expand_unitcell_dev(gpa_plan* p, const double* cell_dev, const gpa_ucell
   UcellGeom g;
   TRY(check_geom(p, geom, "gpa_expand_unitcell", &g));
   HIP_TRY(hipSetDevice(p->device));
-  p->ucell.counted = &p->ws_bytes;
   ProfInstall prof(p);
   const hipError_t e = ucell_expand(p->dtype, cell_dev, g, z2, u_dev, p->n0, p->n1, out_dev, p->stream, &p->ucell);
   if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_expand_unitcell: ") + hipGetErrorString(e));
@@ -91,17 +84,13 @@ int gpa_expand_unitcell(gpa_plan* p, const double* cell, const gpa_ucell_geom* g
   TRY(check_geom(p, geom, "gpa_expand_unitcell", &g));
   HIP_TRY(hipSetDevice(p->device));
   const size_t npx = (size_t)p->n0 * p->n1, ncell = (size_t)g.rs0 * g.rs1;
-  p->ucell.counted = &p->ws_bytes;
-  void* stage = nullptr;
-  HIP_TRY(ucell_stage(&p->ucell, ncell * sizeof(double), p->stream, &stage));
-  double* d_cell = (double*)stage;
+  HIP_TRY(p->ucell.stage.reserve(ncell * sizeof(double), p->stream));
+  double* d_cell = p->ucell.stage.as<double>();
   void* d_out = p->d_wnorm;   // (n0 x n1 reals of the plan)
-  int rc = GPA_OK;
-  hipError_t e = hipMemcpyAsync(d_cell, cell, ncell * sizeof(double), hipMemcpyHostToDevice, p->stream);
-  if (e == hipSuccess && u) e = hipMemcpyAsync(p->d_u, u, 2 * npx * p->rsz, hipMemcpyHostToDevice, p->stream);
-  if (e == hipSuccess) rc = gpa_expand_unitcell_dev(p, d_cell, geom, z2, u ? p->d_u : nullptr, d_out);
-  if (e == hipSuccess && rc == GPA_OK) e = hipMemcpyAsync(out, d_out, npx * p->rsz, hipMemcpyDeviceToHost, p->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_expand_unitcell: ") + hipGetErrorString(e));
-  return rc;
+  HIP_TRY(hipMemcpyAsync(d_cell, cell, ncell * sizeof(double), hipMemcpyHostToDevice, p->stream));
+  if (u) HIP_TRY(hipMemcpyAsync(p->d_u, u, 2 * npx * p->rsz, hipMemcpyHostToDevice, p->stream));
+  TRY(gpa_expand_unitcell_dev(p, d_cell, geom, z2, u ? p->d_u : nullptr, d_out));
+  HIP_TRY(hipMemcpyAsync(out, d_out, npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return GPA_OK;
 }

@@ -39,9 +39,9 @@ int gpa_reconstruct_prediff(gpa_plan* p, const void* grads, const void* weights,
   TRY(ensure_tbuf(p, (P + 1) / 2));
   // staging: grads (P x npx x 2 reals = P complex planes) in d_lockin, weights in Tbuf
   HIP_TRY(hipMemcpyAsync(p->d_lockin, grads, (size_t)P * npx * 2 * p->rsz, hipMemcpyHostToDevice, p->stream));
-  HIP_TRY(hipMemcpyAsync(p->Tbuf, weights, (size_t)P * npx * p->rsz, hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipMemcpyAsync(p->Tbuf.ptr, weights, (size_t)P * npx * p->rsz, hipMemcpyHostToDevice, p->stream));
   TRY(stage_kmat(p, kvecs, P));
-  HIP_TRY(launch_prediff(p->dtype, p->d_lockin, p->Tbuf, p->d_kmat, P, p->n0, p->n1, p->d_dudx, p->d_dudy, p->d_wnorm,
+  HIP_TRY(launch_prediff(p->dtype, p->d_lockin, p->Tbuf.ptr, p->d_kmat, P, p->n0, p->n1, p->d_dudx, p->d_dudy, p->d_wnorm,
                          p->stream));
   HIP_TRY(hipMemcpyAsync(dudx, p->d_dudx, (size_t)2 * p->n0 * (p->n1 - 1) * p->rsz, hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(hipMemcpyAsync(dudy, p->d_dudy, (size_t)2 * (p->n0 - 1) * p->n1 * p->rsz, hipMemcpyDeviceToHost, p->stream));
@@ -58,9 +58,9 @@ int gpa_weighted_lstsq(gpa_plan* p, const void* b, const void* weights, const do
   // staging: b in d_lockin (P complex planes hold 2P real ones), weights in Tbuf
   TRY(ensure_tbuf(p, (P + 1) / 2));
   HIP_TRY(hipMemcpyAsync(p->d_lockin, b, (size_t)P * npx * p->rsz, hipMemcpyHostToDevice, p->stream));
-  HIP_TRY(hipMemcpyAsync(p->Tbuf, weights, (size_t)P * npx * p->rsz, hipMemcpyHostToDevice, p->stream));
+  HIP_TRY(hipMemcpyAsync(p->Tbuf.ptr, weights, (size_t)P * npx * p->rsz, hipMemcpyHostToDevice, p->stream));
   TRY(stage_kmat(p, kvecs, P));
-  HIP_TRY(launch_wlstsq(p->dtype, p->d_lockin, p->Tbuf, p->d_kmat, P, npx, p->d_u, p->stream));
+  HIP_TRY(launch_wlstsq(p->dtype, p->d_lockin, p->Tbuf.ptr, p->d_kmat, P, npx, p->d_u, p->stream));
   HIP_TRY(hipMemcpyAsync(out, p->d_u, 2 * npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
   HIP_TRY(hipStreamSynchronize(p->stream));
   return GPA_OK;

@@ -36,7 +36,6 @@ int gpa_invert_u_mode_dev(gpa_plan* p, const void* u_dev, double scale, int iter
   TRY(check_invert_args(p, u_dev, out_dev, iters, edge, mode));
   TRY(check_rects(rects, nrect, p->n0 + (overlap ? 2 * edge : 0), p->n1 + (overlap ? 2 * edge : 0), "gpa_invert_u_mode_dev"));
   HIP_TRY(hipSetDevice(p->device));
-  p->warp.counted = &p->ws_bytes;
   ProfInstall prof(p);
   const hipError_t e = overlap ? warp_invert_u(p->dtype, u_dev, p->n0, p->n1, scale, iters, edge, 0, out_dev, p->stream, mode, 1, &p->warp, rects, nrect)
                                : warp_invert_u(p->dtype, u_dev, p->n0, p->n1, scale, iters, 0, edge, out_dev, p->stream, mode, 0, &p->warp, rects, nrect);
@@ -63,7 +62,6 @@ int gpa_undistort_image_scaled_dev(gpa_plan* p, const void* deformed_dev, const 
   ProfInstall prof(p);
   // one reservation for the inversion AND the resampling (the first call used to grow the scratch twice, with a stream
   // synchronisation and a free in between); counted in gpa_plan_workspace_bytes
-  p->warp.counted = &p->ws_bytes;
   HIP_TRY(warp_reserve_undistort(p->dtype, p->n0, p->n1, &p->warp, p->stream));
   void* uinv = uinv_dev ? uinv_dev : p->d_dudx;   // (2 planes of n0 x n1 fit)
   HIP_TRY(warp_invert_u(p->dtype, u_dev, p->n0, p->n1, -scale, 35, 0, 0, uinv, p->stream, 0, 1, &p->warp, rects, nrect));
@@ -87,7 +85,6 @@ int gpa_undistort_image_batch_dev(gpa_plan* p, const void* frames_dev, int B, co
   TRY(check_stack_args(p, frames_dev, B, u_dev, out_dev, "gpa_undistort_image_batch_dev"));
   HIP_TRY(hipSetDevice(p->device));
   ProfInstall prof(p);
-  p->warp.counted = &p->ws_bytes;
   void* uinv = uinv_dev ? uinv_dev : (u_per_frame ? nullptr : p->d_dudx);   // (a shared u_inv: 2 planes of n0 x n1 fit)
   HIP_TRY(warp_undistort_stack(p->dtype, frames_dev, B, u_dev, u_per_frame ? 1 : 0, scale, uinv, p->n0, p->n1, out_dev, p->stream, &p->warp));
   if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
@@ -102,30 +99,24 @@ int gpa_undistort_image_batch(gpa_plan* p, const void* frames, int B, const void
   const int per = u_per_frame ? 1 : 0;
   const size_t pb = (size_t)p->n0 * p->n1 * p->rsz;
   const int chunk = warp_stack_chunk(p->dtype, p->n0, p->n1, B, per);
-  char* d_stage = nullptr;      // chunk frames | chunk results | chunk fields (per frame)
-  HIP_TRY(hipMalloc(&d_stage, (size_t)chunk * pb * (per ? 4 : 2)));
-  char *d_fr = d_stage, *d_res = d_stage + (size_t)chunk * pb, *d_uf = d_res + (size_t)chunk * pb;
-  p->warp.counted = &p->ws_bytes;
-  hipError_t e = hipSuccess;
-  bool first = true;
-  for (int f0 = 0; f0 < B && e == hipSuccess; f0 += chunk, first = false) {
+  DevBuf stage;   // a temporary of this call: chunk frames | chunk results | chunk fields (per frame)
+  HIP_TRY(stage.reserve((size_t)chunk * pb * (per ? 4 : 2), p->stream));
+  char *d_fr = stage.as<char>(), *d_res = d_fr + (size_t)chunk * pb, *d_uf = d_res + (size_t)chunk * pb;
+  for (int f0 = 0; f0 < B; f0 += chunk) {
     const int nb = std::min(chunk, B - f0);
-    e = hipMemcpyAsync(d_fr, (const char*)frames + (size_t)f0 * pb, (size_t)nb * pb, hipMemcpyHostToDevice, p->stream);
+    HIP_TRY(hipMemcpyAsync(d_fr, (const char*)frames + (size_t)f0 * pb, (size_t)nb * pb, hipMemcpyHostToDevice, p->stream));
     const void* d_u = nullptr;   // (shared field after the first chunk: p->d_dudx holds its inverse)
-    if (e == hipSuccess && per) {
-      e = hipMemcpyAsync(d_uf, (const char*)u + 2 * (size_t)f0 * pb, 2 * (size_t)nb * pb, hipMemcpyHostToDevice, p->stream);
+    if (per) {
+      HIP_TRY(hipMemcpyAsync(d_uf, (const char*)u + 2 * (size_t)f0 * pb, 2 * (size_t)nb * pb, hipMemcpyHostToDevice, p->stream));
       d_u = d_uf;
-    } else if (e == hipSuccess && first) {
-      e = hipMemcpyAsync(p->d_u, u, 2 * pb, hipMemcpyHostToDevice, p->stream);
+    } else if (f0 == 0) {
+      HIP_TRY(hipMemcpyAsync(p->d_u, u, 2 * pb, hipMemcpyHostToDevice, p->stream));
       d_u = p->d_u;
     }
-    if (e == hipSuccess)
-      e = warp_undistort_stack(p->dtype, d_fr, nb, d_u, per, 1.0, per ? nullptr : p->d_dudx, p->n0, p->n1, d_res, p->stream, &p->warp);
-    if (e == hipSuccess) e = hipMemcpyAsync((char*)out + (size_t)f0 * pb, d_res, (size_t)nb * pb, hipMemcpyDeviceToHost, p->stream);
-    if (e == hipSuccess) e = hipStreamSynchronize(p->stream);   // (pageable memory: the copies are synchronous anyway)
+    HIP_TRY(warp_undistort_stack(p->dtype, d_fr, nb, d_u, per, 1.0, per ? nullptr : p->d_dudx, p->n0, p->n1, d_res, p->stream, &p->warp));
+    HIP_TRY(hipMemcpyAsync((char*)out + (size_t)f0 * pb, d_res, (size_t)nb * pb, hipMemcpyDeviceToHost, p->stream));
+    HIP_TRY(hipStreamSynchronize(p->stream));   // (pageable memory: the copies are synchronous anyway)
   }
-  (void)hipFree(d_stage);
-  if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_undistort_image_batch: ") + hipGetErrorString(e));
   return GPA_OK;
 }
 
@@ -134,16 +125,13 @@ static int invert_u_host(gpa_plan* p, const void* u, int iters, int edge, int ov
   HIP_TRY(hipSetDevice(p->device));
   const int e2 = overlap ? edge : 0;
   const size_t npx = (size_t)p->n0 * p->n1, nout = (size_t)(p->n0 + 2 * e2) * (p->n1 + 2 * e2);
-  void* d_out = nullptr;
-  HIP_TRY(hipMalloc(&d_out, 2 * nout * p->rsz));
-  int rc = GPA_OK;
-  hipError_t e = hipMemcpyAsync(p->d_u, u, 2 * npx * p->rsz, hipMemcpyHostToDevice, p->stream);
-  if (e == hipSuccess) rc = gpa_invert_u_mode_dev(p, p->d_u, 1.0, iters, edge, overlap, mode, nullptr, 0, d_out);
-  if (e == hipSuccess && rc == GPA_OK) e = hipMemcpyAsync(out, d_out, 2 * nout * p->rsz, hipMemcpyDeviceToHost, p->stream);
-  if (e == hipSuccess) e = hipStreamSynchronize(p->stream);
-  (void)hipFree(d_out);
-  if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_invert_u: ") + hipGetErrorString(e));
-  return rc;
+  DevBuf d_out;   // a temporary of this call
+  HIP_TRY(d_out.reserve(2 * nout * p->rsz, p->stream));
+  HIP_TRY(hipMemcpyAsync(p->d_u, u, 2 * npx * p->rsz, hipMemcpyHostToDevice, p->stream));
+  TRY(gpa_invert_u_mode_dev(p, p->d_u, 1.0, iters, edge, overlap, mode, nullptr, 0, d_out.ptr));
+  HIP_TRY(hipMemcpyAsync(out, d_out.ptr, 2 * nout * p->rsz, hipMemcpyDeviceToHost, p->stream));
+  HIP_TRY(hipStreamSynchronize(p->stream));
+  return GPA_OK;
 }
 
 int gpa_invert_u_overlap(gpa_plan* p, const void* u, int iters, int edge, void* out) {

@@ -14,6 +14,8 @@
 #include <hip/hip_runtime.h>
 #include <stddef.h>
 
+#include "gpa_devbuf.h"
+
 namespace gpa {
 
 enum DftKind { DFT_NONE = 0, DFT_POW2 = 1, DFT_BLUE = 2, DFT_BIG = 3 };
@@ -30,11 +32,8 @@ struct DftAxis {
 
 // scratch of the BIG engine (lines x L complex), kept by the plan and grown on demand
 struct DftWork {
-  void* buf = nullptr;
-  size_t cap = 0;
-  size_t* counted = nullptr;      // where the owner accounts its bytes (gpa_plan::ws_bytes), may be null
+  DevBuf buf;   // the owner sets buf.counted
 };
-void dft_work_free(DftWork* w);
 
 // force: 0 = choose, DFT_BLUE / DFT_BIG = that engine if it can take n (tests); returns hipErrorInvalidValue if n is out of range
 hipError_t dft_axis_create(int dtype, int n, hipStream_t s, DftAxis* out, size_t* bytes, int force = 0);

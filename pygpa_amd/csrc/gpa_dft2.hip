@@ -531,23 +531,6 @@ hipError_t big_launch(const DftAxis& a, cpx<T>* Z, size_t zpitch, int nlines, cp
   return hipGetLastError();
 }
 
-hipError_t work_reserve(DftWork* w, size_t bytes, hipStream_t s) {
-  if (!w) return hipErrorInvalidValue;
-  if (w->cap >= bytes) return hipSuccess;
-  hipError_t e;
-  if (w->buf) {
-    if ((e = hipStreamSynchronize(s)) != hipSuccess) return e;
-    (void)hipFree(w->buf);
-    if (w->counted) *w->counted -= w->cap;
-    w->buf = nullptr;
-    w->cap = 0;
-  }
-  if ((e = hipMalloc(&w->buf, bytes)) != hipSuccess) return e;
-  w->cap = bytes;
-  if (w->counted) *w->counted += bytes;
-  return hipSuccess;
-}
-
 // lines of length a.n: COLS -> `nlines` columns of a row-major array with row pitch `pitch`; rows -> `nlines` rows
 template <class T>
 hipError_t big_run(const DftAxis& a, bool cols, cpx<T>* Z, size_t pitch, int nlines, DftWork* w, hipStream_t s) {
@@ -558,9 +541,9 @@ hipError_t big_run(const DftAxis& a, bool cols, cpx<T>* Z, size_t pitch, int nli
   if (chunk < (cols ? 64 : 1)) chunk = cols ? 64 : 1;
   if (chunk > (size_t)nlines) chunk = nlines;
   if (!cols && chunk > 32768) chunk = 32768;   // (grid.y)
-  hipError_t e = work_reserve(w, chunk * L * sizeof(cpx<T>), s);
+  hipError_t e = w ? w->buf.reserve(chunk * L * sizeof(cpx<T>), s) : hipErrorInvalidValue;
   if (e != hipSuccess) return e;
-  cpx<T>* W = (cpx<T>*)w->buf;
+  cpx<T>* W = w->buf.as<cpx<T>>();
   for (size_t l0 = 0; l0 < (size_t)nlines; l0 += chunk) {
     const int nl = (int)(l0 + chunk <= (size_t)nlines ? chunk : nlines - l0);
     if (cols) e = big_launch<T, true>(a, Z + l0, pitch, nl, W, (size_t)nl, s);
@@ -738,15 +721,6 @@ void dft_axis_destroy(DftAxis* a) {
   for (void* p : {a->tw, a->chirp, a->bspec, a->tw1, a->tw2})
     if (p) (void)hipFree(p);
   *a = DftAxis{};
-}
-
-void dft_work_free(DftWork* w) {
-  if (w->buf) {
-    (void)hipFree(w->buf);
-    if (w->counted) *w->counted -= w->cap;
-  }
-  w->buf = nullptr;
-  w->cap = 0;
 }
 
 hipError_t dft2_inplace(int dtype, const DftAxis& a0, const DftAxis& a1, void* Z, DftWork* w, hipStream_t s) {

@@ -3,6 +3,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "gpa_devbuf.h"
 #include "gpa_fft.h"
 #include "gpa_mrfft.h"
 
@@ -312,13 +313,10 @@ hipError_t launch_stitch(int dtype, const void* tiles, size_t slot_stride, size_
 // with cval = NaN as invert_u_overlap does (geometric_phase_analysis.py:296-299), invert_u never does (:255-258)
 // scratch + prefilter taps of the warp kernels, kept by the plan: no allocation and no host synchronisation per call
 struct WarpWs {
-  void* buf = nullptr;
-  size_t cap = 0;
-  void* taps = nullptr;
+  DevBuf buf;    // scratch, grown on demand; the owner sets buf.counted
+  DevBuf taps;   // allocated once, not counted
   int taps_dtype = -1;
-  size_t* counted = nullptr;   // where the owner accounts the scratch (gpa_plan::ws_bytes), may be null
 };
-void warp_ws_free(WarpWs* ws);
 // scratch of one undistort_image call on an n0 x n1 grid (inversion + resampling): reserved in ONE allocation up front
 hipError_t warp_reserve_undistort(int dtype, int n0, int n1, WarpWs* ws, hipStream_t s);
 // rects = nrect x {r0, c0, h, w}: the windows of the output grid that are computed (nrect = 0: all of it) -- the tiles a
@@ -346,16 +344,10 @@ struct UcellGeom {
 // scratch of the average (sorted pixel lists, per-list sums) and of the expansion (the cell's spline coefficients),
 // kept by the plan and grown on first use
 struct UcellWs {
-  void* buf = nullptr;
-  size_t cap = 0;
+  DevBuf buf;
   WarpWs spline{};             // prefilter taps (buf unused)
-  void* stage = nullptr;       // device staging of the host-pointer entry points
-  size_t stage_cap = 0;
-  size_t* counted = nullptr;
+  DevBuf stage;                // device staging of the host-pointer entry points
 };
-void ucell_ws_free(UcellWs* ws);
-// the staging buffer of ws, at least `bytes` (grown with a stream synchronisation when a call needs more)
-hipError_t ucell_stage(UcellWs* ws, size_t bytes, hipStream_t s, void** out);
 // frames of one batched average: gridDim.y of its sum and finish kernels
 constexpr int UCELL_MAX_FRAMES = 65535;
 // bins of the cell (rs0 x rs1) a plan supports: the keys are int32 with room for the border row and column

@@ -120,7 +120,10 @@ struct gpa_plan {
   Axis ax0_full{}, ax1_full{};    // the plan's largest geometry (L >= 2n - 1): what the tables are sized for
   hipStream_t stream = nullptr;
   size_t rsz = 4, csz = 8;        // bytes per real / complex element
-  size_t ws_bytes = 0;
+  // Memory.  Every device buffer of the plan is a DevBuf (gpa_devbuf.h) that reports to ws_bytes and frees itself with the
+  // plan: the fixed and allocate-once ones sit in `owned` (dmalloc hands out their pointers), the grown ones are members.
+  size_t ws_bytes = 0;            // gpa_plan_workspace_bytes: device bytes of all of them and of the unwrap workspaces
+  std::vector<DevBuf> owned;
   // device buffers
   void* tw0 = nullptr;            // twiddle tables exp(-2 pi i t / L)
   void* tw1 = nullptr;
@@ -147,16 +150,16 @@ struct gpa_plan {
   bool lk_raw = false;            // the last passB_select left the lock-ins raw (fused driver): the consumer applies d_ystep
   bool sh_built_ok = false;       // the tables of that key are complete and worth using
   bool sh_use = false;            // ... and the staged candidates form runs of >= 2 on an x-plane
-  size_t sh_gb_bytes = 0, sh_psi_bytes = 0;
+  DevBuf sh_Gb{&ws_bytes}, sh_psi{&ws_bytes}, sh_pre{&ws_bytes};   // behind sh.Gb / sh.psi / sh.pre, grown on demand
   // y-spectral sweep: pass A filters columns of FFT_y(image), pass B runs no forward transform
   bool ys_ok = false;             // the staged list / rows can take it (built with the shared tables)
   bool ys_use = false;            // ... and the sweep being staged does (sweep_choose_path; NO_YSPEC=1 keeps the spatial path)
   PassAYspec ys{};                // Yhat / strips (grown on demand, ensure_yspec), the (block, planes) groups of the staged list
   int* d_ys_groups = nullptr;     // [16 max_batch][4]: the plane list (16 max_batch entries), behind it 3 ints per group
   int ys_gmax = 0;                // the cap (YSPEC_GROUP) the staged groups were cut with
-  size_t ys_yhat_bytes = 0, ys_strips_bytes = 0;
+  DevBuf ys_Yhat{&ws_bytes}, ys_strips{&ws_bytes};   // behind ys.Yhat / ys.strips
   std::vector<int> staged_planeof;
-  void* Tbuf = nullptr;           // [tbuf_planes][n0][n1] complex: one plane per DISTINCT wx (x-plane), grown on demand
+  DevBuf Tbuf{&ws_bytes};         // [tbuf_planes][n0][n1] complex: one plane per DISTINCT wx (x-plane), grown on demand
   int tbuf_planes = 0;
   SweepTables tb{};
   double* d_kl = nullptr;         // [max_batch][2]
@@ -164,7 +167,7 @@ struct gpa_plan {
   double* d_pw = nullptr;         // [max_batch] distinct wx values (x-planes)
   int last_planes = 0;
   std::vector<double> staged_kl, staged_kr, staged_kmat;   // what the device tables currently hold
-  int* h_iters = nullptr;         // pinned: iteration counts of the last (possibly asynchronous) driver call
+  DevBuf h_iters{nullptr, true};  // pinned ints: iteration counts of the last (possibly asynchronous) driver call
   int iters_stride = 1;           // 1: two-stream driver (h_iters[0], [1]); 4: paired workspace (flag words of 2 problems)
   int iters_off = 0;              // paired / batched: the word of a problem's flags that holds its count
   // images of up to 1024^2: both components of u in ONE set of launches (blockIdx.z) on one stream -- measured 8 %
@@ -172,16 +175,14 @@ struct gpa_plan {
   // streams win by 4 % (profiles/r02_image_stacks.txt, 'stack of 1')
   UnwrapWorkspace uwp{};
   bool have_uwp = false, use_pair = false;
-  double* h_k = nullptr;          // pinned staging, 4 * max_batch doubles
+  DevBuf h_k{nullptr, true};      // pinned staging, 6 * max_batch + 32 doubles
   void* d_image = nullptr;        // staging for host-pointer entry points
   void* d_mean = nullptr;
   void* d_tile_mean = nullptr;    // whole-image mean of the tile path (gpa_tile_gradients_dev)
-  double* d_tsum_part = nullptr;  // partial sums of gpa_tile_sums_dev, grown on demand
-  size_t tsum_cap = 0;
+  DevBuf d_tsum_part{&ws_bytes};  // partial sums of gpa_tile_sums_dev (doubles), grown on demand
   hipEvent_t ev_x = nullptr;      // stream-to-stream ordering (gpa_plan_wait_stream / gpa_stream_wait_plan)
   double tile_mean = std::numeric_limits<double>::quiet_NaN();
-  void* d_sf = nullptr;           // [K][n0][n1] complex, grown on demand (a4 gradient path)
-  size_t sf_bytes = 0;
+  DevBuf d_sf{&ws_bytes};         // [K][n0][n1] complex, grown on demand (a4 gradient path)
   void* d_grad = nullptr;         // n0 x n1 x 2 staging for the host-pointer a4 call
   void* d_grads = nullptr;        // [max_peaks] n0 x n1 x 2 and
   void* d_absw = nullptr;         // [max_peaks] n0 x n1: staging of gpa_extract_displacement_field_grad, allocated on first use
@@ -201,13 +202,11 @@ struct gpa_plan {
   // batched driver (gpa_extract_displacement_field_batch_dev): one workspace for the 2 x images solves of a call
   UnwrapWorkspace uwb{};
   int uwb_images = 0;
-  void* d_wnorm_b = nullptr;      // images x n0 x n1
-  int* h_iters_b = nullptr;       // pinned: 4 ints per problem
-  // sweep of a chunk of images in one set of launches: x-planes, lock-ins, means, mean scratch per image
-  void *bT = nullptr, *bL = nullptr, *bMean = nullptr;
-  double* bScratch = nullptr;
-  size_t bT_bytes = 0, bL_bytes = 0;
-  int b_chunk = 0;
+  size_t uwb_bytes = 0;           // its device bytes: the one workspace that is rebuilt, so counted beside ws_bytes
+  DevBuf d_wnorm_b{&ws_bytes};    // images x n0 x n1
+  DevBuf h_iters_b{nullptr, true};   // pinned: 4 ints per problem
+  // sweep of a chunk of images in one set of launches: x-planes, lock-ins, means, mean scratch (doubles) per image
+  DevBuf bT{&ws_bytes}, bL{&ws_bytes}, bMean{&ws_bytes}, bScratch{&ws_bytes};
   UnwrapWorkspace uw2{};          // second workspace + stream: the two components of u unwrap concurrently
   hipStream_t stream2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -215,7 +214,7 @@ struct gpa_plan {
   DftWork dftw{};                 // scratch of its through-HBM engine, grown on demand
   void* d_pertab = nullptr;       // a9: per-axis factors 1 - e^(2 pi i j / n) and sin^2(pi j / n) (per_tables_create)
   // f-3: tables of the FFT form of gaussian_filter (gpa_gaussfft.h), two sigmas per axis (difference of Gaussians)
-  struct GaussTab { double sigma = -1.0; int lg = 0; void* H = nullptr; void* tw = nullptr; int cap_lg = 0; unsigned stamp = 0; };
+  struct GaussTab { double sigma = -1.0; int lg = 0; DevBuf H, tw; unsigned stamp = 0; };
   GaussTab gft[2][2];
   unsigned gft_clock = 0;
   double* d_peakws = nullptr;     // f-3: min / max partials (2 x 2048), threshold, candidate counter
@@ -225,10 +224,8 @@ struct gpa_plan {
   UcellWs ucell{};                // scratch of unit-cell averaging / expansion (gpa_ucell.hip), grown on first use
   // a8 iterate_GPA (gpa_api_iterate.hip), grown on demand: the Huber work of the batched plane fit, behind it the driver's
   // amax / psi / weight planes (and the prs / w planes of its host form)
-  void* d_iter = nullptr;
-  size_t iter_bytes = 0;
-  double* h_iter = nullptr;       // pinned: per plane 4 doubles up (coefficients, flag), 10 down (sums)
-  size_t h_iter_planes = 0;
+  DevBuf d_iter{&ws_bytes};
+  DevBuf h_iter{nullptr, true};   // pinned doubles: per plane 4 up (coefficients, flag), 10 down (sums)
   // timing
   hipEvent_t ev0 = nullptr, ev1 = nullptr;
   bool profiling = false;
@@ -244,6 +241,15 @@ struct gpa_plan {
   // downloads overlapped with the next call (gpa_download_async)
   hipStream_t copy_stream = nullptr;
   hipEvent_t ev_dl_ready = nullptr, ev_dl_done[4] = {nullptr, nullptr, nullptr, nullptr};
+
+  // the workspaces and tables that live in structs of their own report to the plan's counter too.  (Hidden: the public header
+  // declares the type inside its visibility pragma, which would export the two.)
+  __attribute__((visibility("hidden"))) ~gpa_plan() = default;
+  __attribute__((visibility("hidden"))) gpa_plan() {
+    warp.buf.counted = ucell.buf.counted = ucell.stage.counted = dftw.buf.counted = &ws_bytes;
+    for (auto& ax : gft)
+      for (auto& g : ax) g.H.counted = g.tw.counted = &ws_bytes;
+  }
 };
 
 template <class T>
@@ -267,6 +273,8 @@ int shared_prepare(gpa_plan* p, int P, int K);
 int stage_kvectors(gpa_plan* p, const double* kl, const double* kr_per_b, int B, int* planes_out);
 int ensure_tbuf(gpa_plan* p, int planes);
 int ensure_sf(gpa_plan* p, size_t bytes);
+// at least `bytes` in a buffer of the plan (DevBuf::reserve on the plan's stream), failing in the words of `what`
+int plan_reserve(gpa_plan* p, DevBuf& b, size_t bytes, const char* what);
 int stage_kmat(gpa_plan* p, const double* kvecs, int P);
 // the x-planes pass B reads: those of one image in the plan's own buffer ({p->Tbuf, 1, 0}), or those of a stack of nimg images
 // `stride` planes apart (stride != 0 marks a stack)

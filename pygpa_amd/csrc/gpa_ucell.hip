@@ -306,20 +306,6 @@ __global__ __launch_bounds__(256) void ucell_expand_kernel(const double* __restr
 
 inline size_t align256(size_t b) { return (b + 255) & ~(size_t)255; }
 
-hipError_t reserve(UcellWs* ws, size_t bytes, hipStream_t s) {
-  if (ws->cap >= bytes) return hipSuccess;
-  hipError_t e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return e;
-  if (ws->buf) (void)hipFree(ws->buf);
-  if (ws->counted) *ws->counted -= ws->cap;
-  ws->buf = nullptr;
-  ws->cap = 0;
-  e = hipMalloc(&ws->buf, bytes);
-  if (e != hipSuccess) return e;
-  ws->cap = bytes;
-  if (ws->counted) *ws->counted += bytes;
-  return hipSuccess;
-}
 
 // exclusive scan of n ints (n <= SCAN_TILE^2); sums: ceil(n / SCAN_TILE) ints of scratch
 hipError_t exclusive_scan(const int* in, int* out, size_t n, int* sums, hipStream_t s) {
@@ -351,9 +337,9 @@ hipError_t average_t(const T* d_images, int B, const T* d_u, int n0, int n1, con
   const size_t b_sums = align256(((nhist + SCAN_TILE - 1) / SCAN_TILE) * sizeof(int));
   const size_t b_start = align256(((size_t)nkeys + 1) * sizeof(int)), b_frac = align256(n * sizeof(double));
   const size_t b_part = align256((size_t)B * nkeys * 8 * sizeof(double));
-  hipError_t e = reserve(ws, 4 * b_int + 2 * b_hist + b_sums + b_start + 2 * b_frac + b_part, s);
+  hipError_t e = ws->buf.reserve(4 * b_int + 2 * b_hist + b_sums + b_start + 2 * b_frac + b_part, s);
   if (e != hipSuccess) return e;
-  char* c = (char*)ws->buf;
+  char* c = (char*)ws->buf.ptr;
   int* kA = (int*)c;
   int* kB = (int*)(c += b_int);
   int* iA = (int*)(c += b_int);
@@ -417,11 +403,11 @@ template <class T>
 hipError_t expand_t(const double* d_cell, const UcellGeom& g, double z2, const T* d_u, int n0, int n1, T* d_out, hipStream_t s,
                     UcellWs* ws) {
   const size_t ncell = (size_t)g.rs0 * g.rs1, b = align256(ncell * sizeof(double));
-  hipError_t e = reserve(ws, 3 * b, s);
+  hipError_t e = ws->buf.reserve(3 * b, s);
   if (e != hipSuccess) return e;
-  double* clean = (double*)ws->buf;
-  double* tmp = (double*)((char*)ws->buf + b);
-  double* coef = (double*)((char*)ws->buf + 2 * b);
+  double* clean = (double*)ws->buf.ptr;
+  double* tmp = (double*)((char*)ws->buf.ptr + b);
+  double* coef = (double*)((char*)ws->buf.ptr + 2 * b);
   {
     GPA_PROF("ucell_nan_to_num_kernel", s);
     nan_to_num_kernel<<<(unsigned)((ncell + 255) / 256), 256, 0, s>>>(d_cell, ncell, clean);
@@ -437,35 +423,6 @@ hipError_t expand_t(const double* d_cell, const UcellGeom& g, double z2, const T
 }
 
 }  // namespace
-
-void ucell_ws_free(UcellWs* ws) {
-  if (ws->buf) (void)hipFree(ws->buf);
-  if (ws->buf && ws->counted) *ws->counted -= ws->cap;
-  if (ws->stage) (void)hipFree(ws->stage);
-  if (ws->stage && ws->counted) *ws->counted -= ws->stage_cap;
-  warp_ws_free(&ws->spline);
-  size_t* counted = ws->counted;
-  *ws = UcellWs{};
-  ws->counted = counted;
-}
-
-// device staging of the host-pointer entry points: grown (stream drained, old buffer freed) only when a call needs more
-hipError_t ucell_stage(UcellWs* ws, size_t bytes, hipStream_t s, void** out) {
-  if (ws->stage_cap < bytes) {
-    hipError_t e = hipStreamSynchronize(s);
-    if (e != hipSuccess) return e;
-    if (ws->stage) (void)hipFree(ws->stage);
-    if (ws->counted) *ws->counted -= ws->stage_cap;
-    ws->stage = nullptr;
-    ws->stage_cap = 0;
-    e = hipMalloc(&ws->stage, bytes);
-    if (e != hipSuccess) return e;
-    ws->stage_cap = bytes;
-    if (ws->counted) *ws->counted += bytes;
-  }
-  *out = ws->stage;
-  return hipSuccess;
-}
 
 hipError_t ucell_average(int dtype, const void* d_images, int B, const void* d_u, int n0, int n1, const UcellGeom& g,
                          double* d_res, double* d_weights, hipStream_t s, UcellWs* ws) {

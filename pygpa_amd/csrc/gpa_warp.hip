@@ -465,33 +465,17 @@ __global__ __launch_bounds__(256) void warp_stack_kernel(const T* __restrict__ c
 template <class T>
 hipError_t ensure_taps(WarpWs* ws, hipStream_t s) {
   const int want = sizeof(T) == 4 ? 0 : 1;
-  if (ws->taps && ws->taps_dtype == want) return hipSuccess;
+  if (ws->taps.ptr && ws->taps_dtype == want) return hipSuccess;
   constexpr int KT = TapHalf<T>::value;
   const double z = sqrt(3.0) - 2.0;
   T h[2 * KT + 1];
   for (int k = -KT; k <= KT; ++k) h[k + KT] = (T)((-6.0 * z / (1.0 - z * z)) * pow(z, abs(k)));
-  hipError_t e = hipSuccess;
-  if (!ws->taps) e = hipMalloc(&ws->taps, (2 * TapHalf<double>::value + 1) * sizeof(double));
+  hipError_t e = ws->taps.reserve((2 * TapHalf<double>::value + 1) * sizeof(double), s);
   if (e != hipSuccess) return e;
-  e = hipMemcpyAsync(ws->taps, h, sizeof(h), hipMemcpyHostToDevice, s);
+  e = hipMemcpyAsync(ws->taps.ptr, h, sizeof(h), hipMemcpyHostToDevice, s);
   if (e != hipSuccess) return e;
   ws->taps_dtype = want;
   return hipStreamSynchronize(s);   // h lives on this stack frame (once per workspace)
-}
-// scratch of at least `bytes`: grown (stream drained, old buffer freed) only when a call needs more than any before it
-hipError_t reserve(WarpWs* ws, size_t bytes, hipStream_t s) {
-  if (ws->cap >= bytes) return hipSuccess;
-  hipError_t e = hipStreamSynchronize(s);
-  if (e != hipSuccess) return e;
-  if (ws->buf) (void)hipFree(ws->buf);
-  if (ws->counted) *ws->counted -= ws->cap;
-  ws->buf = nullptr;
-  ws->cap = 0;
-  e = hipMalloc(&ws->buf, bytes);
-  if (e != hipSuccess) return e;
-  ws->cap = bytes;
-  if (ws->counted) *ws->counted += bytes;
-  return hipSuccess;
 }
 
 // coefficients of `in` (m0 x m1); tmp: same size.  npad >= 0: `in` is the unpadded (m0 - 2 npad) x (m1 - 2 npad) field, padded
@@ -532,11 +516,11 @@ template <class T>
 hipError_t invert_constant_t(const T* d_u, int n0, int n1, T scale, int iters, int edge, int shift, int nan_last, T* d_out,
                              hipStream_t s, WarpWs* ws, const int* rects, int nrect) {
   const size_t npx = (size_t)n0 * n1;
-  hipError_t e = reserve(ws, 4 * npx * sizeof(T), s);   // scaled copy, tmp, coef0, coef1
+  hipError_t e = ws->buf.reserve(4 * npx * sizeof(T), s);   // scaled copy, tmp, coef0, coef1
   if (e == hipSuccess) e = ensure_taps<T>(ws, s);
   if (e != hipSuccess) return e;
-  T* buf = (T*)ws->buf;
-  const T* d_h = (const T*)ws->taps;
+  T* buf = (T*)ws->buf.ptr;
+  const T* d_h = (const T*)ws->taps.ptr;
   T *tmp = buf + npx, *c0 = buf + 2 * npx, *c1 = buf + 3 * npx;
   for (int c = 0; c < 2 && e == hipSuccess; ++c)
     e = prefilter<T>(d_u + (size_t)c * npx, n0, n1, EXT_MIRROR, d_h, tmp, c == 0 ? c0 : c1, s, 0, scale);
@@ -568,11 +552,11 @@ template <class T>
 hipError_t invert_folded_t(const T* d_u, int n0, int n1, T scale, int iters, int edge, int shift, int ext, T* d_out, hipStream_t s,
                            WarpWs* ws, const int* rects, int nrect) {
   const size_t npx = (size_t)n0 * n1;
-  hipError_t e = reserve(ws, 4 * npx * sizeof(T), s);   // scaled copy, tmp, coef0, coef1
+  hipError_t e = ws->buf.reserve(4 * npx * sizeof(T), s);   // scaled copy, tmp, coef0, coef1
   if (e == hipSuccess) e = ensure_taps<T>(ws, s);
   if (e != hipSuccess) return e;
-  T* buf = (T*)ws->buf;
-  const T* d_h = (const T*)ws->taps;
+  T* buf = (T*)ws->buf.ptr;
+  const T* d_h = (const T*)ws->taps.ptr;
   T *tmp = buf + npx, *c0 = buf + 2 * npx, *c1 = buf + 3 * npx;
   for (int c = 0; c < 2 && e == hipSuccess; ++c)
     e = prefilter<T>(d_u + (size_t)c * npx, n0, n1, ext, d_h, tmp, c == 0 ? c0 : c1, s, 0, scale);
@@ -624,11 +608,11 @@ hipError_t invert_t(const T* d_u, int n0, int n1, T scale, int iters, int edge, 
                     const int* rects, int nrect) {
   const int m0 = n0 + 2 * NPAD, m1 = n1 + 2 * NPAD;
   const size_t mp = (size_t)m0 * m1;
-  hipError_t e = reserve(ws, 4 * mp * sizeof(T), s);   // padded, tmp, coef0, coef1
+  hipError_t e = ws->buf.reserve(4 * mp * sizeof(T), s);   // padded, tmp, coef0, coef1
   if (e == hipSuccess) e = ensure_taps<T>(ws, s);
   if (e != hipSuccess) return e;
-  T* buf = (T*)ws->buf;
-  const T* d_h = (const T*)ws->taps;
+  T* buf = (T*)ws->buf.ptr;
+  const T* d_h = (const T*)ws->taps.ptr;
   T *tmp = buf + mp, *c0 = buf + 2 * mp, *c1 = buf + 3 * mp;
   // (scaling and the 12-sample edge padding of mode 'nearest' happen while the row pass loads its tiles)
   for (int c = 0; c < 2 && e == hipSuccess; ++c)
@@ -643,11 +627,11 @@ hipError_t warp_t(const T* d_img, const T* d_uinv, int n0, int n1, T* d_out, hip
   // (its own scratch region BEHIND what an inversion of this shape uses: undistort_image inverts and warps back to back on
   //  one stream, and a second workspace user must not shrink the first)
   const size_t inv_bytes = 4 * (size_t)(n0 + 2 * NPAD) * (n1 + 2 * NPAD) * sizeof(T);
-  hipError_t e = reserve(ws, inv_bytes + 2 * npx * sizeof(T), s);
+  hipError_t e = ws->buf.reserve(inv_bytes + 2 * npx * sizeof(T), s);
   if (e == hipSuccess) e = ensure_taps<T>(ws, s);
   if (e != hipSuccess) return e;
-  T* buf = (T*)((char*)ws->buf + inv_bytes);
-  e = prefilter<T>(d_img, n0, n1, EXT_MIRROR, (const T*)ws->taps, buf, buf + npx, s);
+  T* buf = (T*)((char*)ws->buf.ptr + inv_bytes);
+  e = prefilter<T>(d_img, n0, n1, EXT_MIRROR, (const T*)ws->taps.ptr, buf, buf + npx, s);
   if (e == hipSuccess) {
     for (int q = 0; q < (nrect > 0 ? nrect : 1); ++q) {
       const Win v = window(nrect > 0 ? rects + 4 * q : nullptr, n0, n1);
@@ -720,12 +704,12 @@ hipError_t undistort_stack_t(const T* d_frames, int B, const T* d_u, int per_fra
   const size_t npx = (size_t)n0 * n1, mp = (size_t)m0 * m1;
   const int chunk = stack_chunk(sizeof(T), n0, n1, B, per_frame);
   const size_t lead = stack_lead_bytes(sizeof(T), n0, n1, per_frame);
-  // ONE reservation for the inversion and the chunks (the inversion's own reserve() then finds the scratch large enough)
-  hipError_t e = reserve(ws, lead + (size_t)chunk * stack_frame_elems(n0, n1, per_frame) * sizeof(T), s);
+  // ONE reservation for the inversion and the chunks (the inversion's own reservation then finds the scratch large enough)
+  hipError_t e = ws->buf.reserve(lead + (size_t)chunk * stack_frame_elems(n0, n1, per_frame) * sizeof(T), s);
   if (e == hipSuccess) e = ensure_taps<T>(ws, s);
   if (e != hipSuccess) return e;
-  const T* d_h = (const T*)ws->taps;
-  T* buf = (T*)((char*)ws->buf + lead);
+  const T* d_h = (const T*)ws->taps.ptr;
+  T* buf = (T*)((char*)ws->buf.ptr + lead);
   if (!per_frame) {
     // one field for all frames: inverted ONCE, as undistort_image inverts it (35 rounds, mode 'nearest', no edge)
     if (d_u) e = invert_t<T>(d_u, n0, n1, -scale, 35, 0, 0, d_uinv, s, ws, nullptr, 0);
@@ -764,16 +748,7 @@ hipError_t warp_undistort_stack(int dtype, const void* d_frames, int B, const vo
 
 hipError_t warp_reserve_undistort(int dtype, int n0, int n1, WarpWs* ws, hipStream_t s) {
   const size_t rs = dtype == 0 ? 4 : 8;
-  return reserve(ws, 4 * (size_t)(n0 + 2 * NPAD) * (n1 + 2 * NPAD) * rs + 2 * (size_t)n0 * n1 * rs, s);
-}
-
-void warp_ws_free(WarpWs* ws) {
-  if (ws->buf) (void)hipFree(ws->buf);
-  if (ws->buf && ws->counted) *ws->counted -= ws->cap;
-  if (ws->taps) (void)hipFree(ws->taps);
-  size_t* counted = ws->counted;
-  *ws = WarpWs{};
-  ws->counted = counted;
+  return ws->buf.reserve(4 * (size_t)(n0 + 2 * NPAD) * (n1 + 2 * NPAD) * rs + 2 * (size_t)n0 * n1 * rs, s);
 }
 
 // d_u: 2 x n0 x n1 (device); the field that is inverted is scale * u; d_out: 2 x (n0+2e) x (n1+2e).  Enqueued on s, no
@@ -797,7 +772,7 @@ hipError_t warp_invert_u(int dtype, const void* d_u, int n0, int n1, double scal
 hipError_t spline_coef_constant_f64(const double* d_in, int n0, int n1, double* d_tmp, double* d_out, hipStream_t s, WarpWs* ws) {
   const hipError_t e = ensure_taps<double>(ws, s);
   if (e != hipSuccess) return e;
-  return prefilter<double>(d_in, n0, n1, EXT_MIRROR, (const double*)ws->taps, d_tmp, d_out, s);
+  return prefilter<double>(d_in, n0, n1, EXT_MIRROR, (const double*)ws->taps.ptr, d_tmp, d_out, s);
 }
 // resample d_img (n0 x n1) at r + u_inv(r), order 3, mode='constant', cval=0
 hipError_t warp_image(int dtype, const void* d_img, const void* d_uinv, int n0, int n1, void* d_out, hipStream_t s, WarpWs* ws,
