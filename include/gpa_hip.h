@@ -506,6 +506,25 @@ int gpa_expand_unitcell(gpa_plan* plan, const double* cell, const gpa_ucell_geom
 int gpa_expand_unitcell_dev(gpa_plan* plan, const double* cell_dev, const gpa_ucell_geom* geom, double z2,
                             const void* u_dev, void* out_dev);
 
+/* Windowed Fourier filtering, wff (geometric_phase_analysis.py:551-580), in its separable form: for every threshold t
+ *   out_t = scale * sum_wx Cx[kx] ( sum_wy Cy[ky] ( keep_t ( Cy[ky] ( Cx[kx] image ) ) ) )
+ * with the window s = round(2 sigma) (halves to even, as Python rounds), offsets j = -s .. s - 1, g(j) = exp(-j^2 / 2 sigma^2),
+ * kx(j) = g(j) e^(i wx j) along axis 1, ky(j) = g(j) e^(i wy j) / sum g^2 along axis 0, scipy.ndimage's 'reflect' boundary, and
+ * keep_t(sf) = sf where |sf| >= thresholds[t], else 0 -- decided as |sf|^2 >= thresholds[t]^2 in the plan's precision; a
+ * negative threshold keeps every sample.  image: n0 x n1 interleaved complex of the plan's dtype; wxs[Kx], wys[Ky],
+ * thresholds[T]: doubles (the reference passes np.arange(wl, wu + wi / 2, wi), wi = 1 / sigma, for both lists and
+ * scale = wi^2 / 4 pi^2); out: T x n0 x n1 interleaved complex, not overlapping image.  Limits of one call, GPA_ERR_ARG
+ * beyond: s <= GPA_WFF_MAX_S, T <= GPA_WFF_MAX_T (split longer threshold lists).  Null pointers, Kx / Ky / T < 1,
+ * sigma <= 0 and non-finite values are GPA_ERR_ARG before a device is touched.  The sums run in a fixed order: the same
+ * bits on every call, and a call with T thresholds gives the planes of T calls with one.
+ * _dev: device pointers, enqueued on the plan's stream (one host synchronisation, for the tap tables).                */
+#define GPA_WFF_MAX_S 40
+#define GPA_WFF_MAX_T 8
+int gpa_wff(gpa_plan* plan, const void* image, double sigma, const double* wxs, int Kx, const double* wys, int Ky,
+            const double* thresholds, int T, double scale, void* out);
+int gpa_wff_dev(gpa_plan* plan, const void* image_dev, double sigma, const double* wxs, int Kx, const double* wys, int Ky,
+                const double* thresholds, int T, double scale, void* out_dev);
+
 /* timing hooks used by bench.py: elapsed milliseconds between two recorded
  * events on the plan's stream (HIP events, so it measures the stream the
  * kernels are launched on).                                                   */

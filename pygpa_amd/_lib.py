@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get('GPA_HIP_LIB') or os.path.join(_HERE, 'libgpa_hip.so')
 GPA_F32, GPA_F64 = 0, 1
 UCELL_MAX_FRAMES = 65535     # frames of one gpa_unit_cell_average_batch_dev call
 UNDISTORT_MAX_FRAMES = 65535     # frames of one gpa_undistort_image_batch[_dev] call
+WFF_MAX_S, WFF_MAX_T = 40, 8     # half-window round(2 sigma) and thresholds of one gpa_wff[_dev] call
 _DTYPES = {GPA_F32: (np.float32, np.complex64), GPA_F64: (np.float64, np.complex128)}
 
 # every symbol of include/gpa_hip.h: name -> (restype, argtypes)
@@ -104,6 +105,8 @@ SIGNATURES = {
     'gpa_unit_cell_average_batch_dev': (_i, [_vp, _vp, _i, _vp, _vp, _vp, _vp]),
     'gpa_expand_unitcell': (_i, [_vp, _vp, _vp, _d, _vp, _vp]),
     'gpa_expand_unitcell_dev': (_i, [_vp, _vp, _vp, _d, _vp, _vp]),
+    'gpa_wff': (_i, [_vp, _vp, _d, _vp, _i, _vp, _i, _vp, _i, _d, _vp]),
+    'gpa_wff_dev': (_i, [_vp, _vp, _d, _vp, _i, _vp, _i, _vp, _i, _d, _vp]),
     'gpa_timer_start': (_i, [_vp]),
     'gpa_timer_stop': (_i, [_vp, _vp]),
     'gpa_set_profiling': (_i, [_vp, _i]),
@@ -508,6 +511,26 @@ class Plan:
         check(self.lib.gpa_expand_unitcell_dev(self.handle, _ptr(int(cell_ptr)), C.byref(geom), float(z2),
                                                _ptr(u_ptr), _ptr(int(out_ptr))),
               'gpa_expand_unitcell_dev')
+
+    # ---- windowed Fourier filtering (geometric_phase_analysis.py:551-580) ----------------------------------
+    def wff(self, image, sigma, wxs, wys, thresholds, scale):
+        """gpa_wff: the filtered fields of up to WFF_MAX_T thresholds, (T,) + shape complex in the plan's precision; image is
+        taken as complex, wxs / wys are the frequency lists along axis 1 / axis 0"""
+        image = np.ascontiguousarray(image, dtype=self.cdtype)
+        if image.shape != self.shape:
+            raise ValueError('image shape %s does not match the plan %s' % (image.shape, self.shape))
+        wxs, wys, thr = _f64(wxs).ravel(), _f64(wys).ravel(), _f64(thresholds).ravel()
+        out = np.empty((len(thr),) + self.shape, dtype=self.cdtype)
+        check(self.lib.gpa_wff(self.handle, _ptr(image), float(sigma), _ptr(wxs), len(wxs), _ptr(wys), len(wys), _ptr(thr),
+                               len(thr), float(scale), _ptr(out)), 'gpa_wff')
+        return out
+
+    def wff_dev(self, image_ptr, out_ptr, sigma, wxs, wys, thresholds, scale):
+        """gpa_wff_dev: image_ptr -> n0 x n1 complex, out_ptr -> T x n0 x n1 complex, both on the device in the plan's precision
+        and not overlapping; enqueued on the plan's stream"""
+        wxs, wys, thr = _f64(wxs).ravel(), _f64(wys).ravel(), _f64(thresholds).ravel()
+        check(self.lib.gpa_wff_dev(self.handle, _ptr(int(image_ptr)), float(sigma), _ptr(wxs), len(wxs), _ptr(wys), len(wys),
+                                   _ptr(thr), len(thr), float(scale), _ptr(int(out_ptr))), 'gpa_wff_dev')
 
     @staticmethod
     def _rects(rects):

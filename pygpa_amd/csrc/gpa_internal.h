@@ -359,4 +359,11 @@ hipError_t ucell_average(int dtype, const void* d_images, int B, const void* d_u
 hipError_t ucell_expand(int dtype, const double* d_cell, const UcellGeom& g, double z2, const void* d_u, int n0, int n1,
                         void* d_out, hipStream_t s, UcellWs* ws);
 
+// ---- windowed Fourier filtering (gpa_wff.hip; geometry and limits: gpa_wff.h) ------------------------------------------
+// img: n0 x n1 complex (dtype); txr: [Kx][2 s], tyr: [Ky][2 s rounded up to wff_block] reversed complex taps, thr2: wff_tslots(T)
+// squared thresholds, all in dtype; A: one complex plane, B: T planes of scratch; out: T x n0 x n1 complex.  Three launches per
+// wx, enqueued on st.  hipErrorInvalidValue where (s, T) is outside the limits of wff_tile.
+hipError_t wff_run(int dtype, const void* d_img, int n0, int n1, int s, const void* d_txr, int Kx, const void* d_tyr, int Ky,
+                   const void* d_thr2, int T, double scale, void* d_A, void* d_B, void* d_out, hipStream_t st);
+
 }  // namespace gpa

@@ -222,6 +222,9 @@ struct gpa_plan {
   bool peaks_smooth_valid = false;
   WarpWs warp{};                  // scratch + taps of the Lawler-Fujita kernels (gpa_warp.hip), grown on first use
   UcellWs ucell{};                // scratch of unit-cell averaging / expansion (gpa_ucell.hip), grown on first use
+  // windowed Fourier filtering (gpa_api_wff.hip), grown on demand: tap tables, the A plane and the T planes B of a call;
+  // device staging of the host-pointer form (image, T output planes)
+  DevBuf wff{&ws_bytes}, wff_stage{&ws_bytes};
   // a8 iterate_GPA (gpa_api_iterate.hip), grown on demand: the Huber work of the batched plane fit, behind it the driver's
   // amax / psi / weight planes (and the prs / w planes of its host form)
   DevBuf d_iter{&ws_bytes};

@@ -157,6 +157,64 @@ def wfr4(image, sigma, klist, kref, dk, dtype=None):
     return {'w': w, 'lockin': lockin, 'kidx': kidx}
 
 
+# --------------------------------------------------------------------------- windowed Fourier filtering
+def _wff_lists(sigma, threshold, wl, wu):
+    """(sigma, thresholds (T,) float64, frequency list, scale) of a wff call, checked on the host.  The list is the
+    reference's np.arange(wl, wu + wi / 2, wi), wi = 1 / sigma: its length depends on float rounding, so it is built here
+    and handed down as it is (geometric_phase_analysis.py:567-570); scale = wi^2 / 4 pi^2 (:579)."""
+    sigma = float(sigma)
+    if not np.isfinite(sigma) or sigma <= 0:
+        raise ValueError('sigma must be a finite number > 0, not %r' % (sigma,))
+    thr = np.atleast_1d(np.asarray(threshold, dtype=np.float64)).ravel()
+    if len(thr) < 1:
+        raise ValueError('threshold must hold at least one value')
+    if not np.all(np.isfinite(thr)):
+        raise ValueError('threshold must be finite')
+    wl, wu = float(wl), float(wu)
+    if not (np.isfinite(wl) and np.isfinite(wu)):
+        raise ValueError('wl and wu must be finite')
+    wi = 1 / sigma
+    ws = np.arange(wl, wu + wi / 2, wi)
+    if len(ws) < 1:
+        raise ValueError('the frequency range wl = %r .. wu = %r is empty' % (wl, wu))
+    return sigma, thr, ws, wi * wi / (4 * np.pi ** 2)
+
+
+def _wff_chunks(run, thr):
+    """the planes of all thresholds: one library call per chunk of _lib.WFF_MAX_T of them"""
+    return np.concatenate([run(thr[i:i + _lib.WFF_MAX_T]) for i in range(0, len(thr), _lib.WFF_MAX_T)])
+
+
+def wff(image, sigma, threshold, wl, wu, verbose=False, dtype=None):
+    """Windowed Fourier filtering of a complex field such as exp(i phi) (geometric_phase_analysis.py:551-580): per
+    frequency pair (wx, wy) of np.arange(wl, wu + wi / 2, wi)^2, wi = 1 / sigma, the windowed spectrum sf = image (*) wave
+    is cut to the samples with |sf| >= threshold[i] and convolved with wave again; returns the sums times wi^2 / 4 pi^2,
+    an array of shape (len(threshold),) + image.shape, complex128 (complex64 with dtype=np.float32).
+
+    Runs on the device in the separable form of DESIGN 2.11 (gpa_wff), one call per chunk of 8 thresholds.  Superset of
+    the reference: a real image is promoted to complex (the reference raises UFuncTypeError there).  ``verbose`` is
+    accepted and prints nothing: the reference's per-frequency lines have no counterpart in a single device call."""
+    image = np.asarray(image)
+    if image.ndim != 2:
+        raise ValueError('image must be 2-D')
+    sigma, thr, ws, scale = _wff_lists(sigma, threshold, wl, wu)
+    real = np.float32 if dtype is not None and np.dtype(dtype) in (np.dtype(np.float32), np.dtype(np.complex64)) else np.float64
+    plan = _lib.get_plan(image.shape, 1, real)
+    return _wff_chunks(lambda t: plan.wff(image, sigma, ws, ws, t, scale), thr)
+
+
+def wff_dev(plan, image_ptr, out_ptr, sigma, threshold, wl, wu, verbose=False):
+    """wff of a field that is resident on the device (`plan`: a _lib.Plan of its shape; `image_ptr`: device pointer to n0 x n1
+    complex values of the plan's precision, not modified; `out_ptr`: device pointer to len(threshold) x n0 x n1 complex
+    values, not overlapping the image): enqueued on the plan's stream, nothing comes to the host.  Returns the number of
+    planes written."""
+    sigma, thr, ws, scale = _wff_lists(sigma, threshold, wl, wu)
+    plane = plan.shape[0] * plan.shape[1] * np.dtype(plan.cdtype).itemsize
+    for i in range(0, len(thr), _lib.WFF_MAX_T):
+        plan.wff_dev(image_ptr, int(out_ptr) + i * plane, sigma, ws, ws, thr[i:i + _lib.WFF_MAX_T], scale)
+    return len(thr)
+
+
 def generate_klists(pks, dk=None, kmax=1.9, kmin=0.2, sort_list=False):
     """Candidate lists for wfr3 / wfr4 (geometric_phase_analysis.py:865-889).  A fixed 0.005-spaced k-grid covers the
     square of half-width kmax * max|k|; a grid point goes to peak i when it lies in the ring kmin .. kmax (times
