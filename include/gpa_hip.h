@@ -525,6 +525,51 @@ int gpa_wff(gpa_plan* plan, const void* image, double sigma, const double* wxs, 
 int gpa_wff_dev(gpa_plan* plan, const void* image_dev, double sigma, const double* wxs, int Kx, const double* wys, int Ky,
                 const double* thresholds, int T, double scale, void* out_dev);
 
+/* Image preparation (pyGPA/imagetools.py:92-194).  Images are n0 x n1 reals of the plan's dtype; masks are uint8_t planes of
+ * n0 x n1, 0 is false and anything else is true (what is written is 0 or 1).  Each entry point has a host-pointer form and a
+ * _dev form on device pointers.  The _dev forms with small host outputs (lims, rows, cols) synchronise the plan's stream, the
+ * others only enqueue work on it (the first call with a new sigma or r uploads its table and synchronises once).  Null
+ * pointers, sigma <= 0 or not finite, r < 0 or > GPA_PREP_MAX_R and B < 1 are GPA_ERR_ARG, with a message that names the
+ * argument, before a device is touched.  Work space is the plan's and counted in the plan's workspace bytes.
+ *
+ * gauss_homogenize (imagetools.py:92-109):  VV = G(mask ? image : 0) / G(mask),  out = image / VV,  G = scipy.ndimage's
+ * gaussian_filter(sigma): axis 0 then axis 1, radius int(4 sigma + 0.5), 'reflect'.  Where the (2R+1)^2 box of the
+ * reflect-extended mask holds no true sample the reference's VV is NaN (0 / 0): that pattern is reproduced exactly (it is
+ * decided in integers) and VV is NaN there, or nan_scale when use_nan_scale != 0.  Elsewhere VV is held within [min, max] of
+ * the masked samples.  vv_out (nullable) receives VV.  out and vv_out may not overlap image or mask.  Samples outside the
+ * mask may be anything (NaN included); a non-finite sample UNDER the mask yields NaN in VV and out on at least the
+ * reference's (2R+1)^2 box around it, on the FFT route on the whole overlap-save segments that hold it.  Radii from
+ * GAUSS_FFT_MINR (option, default 12) on run as overlap-save FFT convolutions, which need 4 R <= 16384 (f32) / 8192 (f64):
+ * sigma <= 1024 / 512, GPA_ERR_ARG naming sigma beyond; shorter radii run as direct sums (and so does every radius with
+ * 2 R + 1 <= 3072 when the option is set above it).  Rows longer than GPA_PREP_MAX_N1: GPA_ERR_STATE.                    */
+#define GPA_PREP_MAX_R 254
+#define GPA_PREP_MAX_N1 32768
+int gpa_gauss_homogenize(gpa_plan* plan, const void* image, const uint8_t* mask, double sigma, int use_nan_scale,
+                         double nan_scale, void* out, void* vv_out);
+int gpa_gauss_homogenize_dev(gpa_plan* plan, const void* image_dev, const uint8_t* mask_dev, double sigma, int use_nan_scale,
+                             double nan_scale, void* out_dev, void* vv_dev);
+/* hit = [hit |] any over b of (frames[b] == value): frames is B x n0 x n1 of the plan's dtype and value is compared in that
+ * precision (an f32 plan compares against (float)value); a NaN value hits nothing.  accumulate != 0 keeps what hit holds,
+ * so a long stack can be sent in chunks.  generate_mask (imagetools.py:178-185) is the erosion of !hit.              */
+int gpa_mask_any_equal(gpa_plan* plan, const void* frames, int B, double value, int accumulate, uint8_t* hit);
+int gpa_mask_any_equal_dev(gpa_plan* plan, const void* frames_dev, int B, double value, int accumulate, uint8_t* hit_dev);
+/* out = scipy.ndimage.binary_erosion(invert ? !in : in, structure = skimage.morphology.disk(r)), border_value 0: the mask is
+ * eaten from the image edges too; r = 0 is the identity; out may be in.  0 <= r <= GPA_PREP_MAX_R.                      */
+int gpa_mask_erode_disk(gpa_plan* plan, const uint8_t* in, int invert, int r, uint8_t* out);
+int gpa_mask_erode_disk_dev(gpa_plan* plan, const uint8_t* in_dev, int invert, int r, uint8_t* out_dev);
+/* lims = { first row, last row + 1, first column, last column + 1 } with a true sample (cull_by_mask, imagetools.py:188-194);
+ * an all-false mask gives the empty { n0, 0, n1, 0 }.  lims is a host array in both forms.                               */
+int gpa_mask_bounds(gpa_plan* plan, const uint8_t* mask, int32_t* lims);
+int gpa_mask_bounds_dev(gpa_plan* plan, const uint8_t* mask_dev, int32_t* lims);
+/* rows[n0], cols[n1] (host arrays in both forms): 1 where every sample of the line is NaN (trim_nans, imagetools.py:128-142) */
+int gpa_nan_lines(gpa_plan* plan, const void* image, uint8_t* rows, uint8_t* cols);
+int gpa_nan_lines_dev(gpa_plan* plan, const void* image_dev, uint8_t* rows, uint8_t* cols);
+/* the loop of trim_nans2 (imagetools.py:145-175), run on the device: lims = { x0, x1, y0, y1 } (host array) of the window
+ * image[x0:x1, y0:y1] it ends with.  A window that empties on the way (an all-NaN image) ends the loop with x1 <= x0 or
+ * y1 <= y0, where the reference fails with an IndexError.                                                               */
+int gpa_nan_trim_lims(gpa_plan* plan, const void* image, int32_t* lims);
+int gpa_nan_trim_lims_dev(gpa_plan* plan, const void* image_dev, int32_t* lims);
+
 /* timing hooks used by bench.py: elapsed milliseconds between two recorded
  * events on the plan's stream (HIP events, so it measures the stream the
  * kernels are launched on).                                                   */

@@ -18,6 +18,7 @@ GPA_F32, GPA_F64 = 0, 1
 UCELL_MAX_FRAMES = 65535     # frames of one gpa_unit_cell_average_batch_dev call
 UNDISTORT_MAX_FRAMES = 65535     # frames of one gpa_undistort_image_batch[_dev] call
 WFF_MAX_S, WFF_MAX_T = 40, 8     # half-window round(2 sigma) and thresholds of one gpa_wff[_dev] call
+PREP_MAX_R, PREP_MAX_N1 = 254, 32768     # erosion radius of gpa_mask_erode_disk, row length of gpa_gauss_homogenize
 _DTYPES = {GPA_F32: (np.float32, np.complex64), GPA_F64: (np.float64, np.complex128)}
 
 # every symbol of include/gpa_hip.h: name -> (restype, argtypes)
@@ -107,6 +108,18 @@ SIGNATURES = {
     'gpa_expand_unitcell_dev': (_i, [_vp, _vp, _vp, _d, _vp, _vp]),
     'gpa_wff': (_i, [_vp, _vp, _d, _vp, _i, _vp, _i, _vp, _i, _d, _vp]),
     'gpa_wff_dev': (_i, [_vp, _vp, _d, _vp, _i, _vp, _i, _vp, _i, _d, _vp]),
+    'gpa_gauss_homogenize': (_i, [_vp, _vp, _vp, _d, _i, _d, _vp, _vp]),
+    'gpa_gauss_homogenize_dev': (_i, [_vp, _vp, _vp, _d, _i, _d, _vp, _vp]),
+    'gpa_mask_any_equal': (_i, [_vp, _vp, _i, _d, _i, _vp]),
+    'gpa_mask_any_equal_dev': (_i, [_vp, _vp, _i, _d, _i, _vp]),
+    'gpa_mask_erode_disk': (_i, [_vp, _vp, _i, _i, _vp]),
+    'gpa_mask_erode_disk_dev': (_i, [_vp, _vp, _i, _i, _vp]),
+    'gpa_mask_bounds': (_i, [_vp, _vp, _vp]),
+    'gpa_mask_bounds_dev': (_i, [_vp, _vp, _vp]),
+    'gpa_nan_lines': (_i, [_vp, _vp, _vp, _vp]),
+    'gpa_nan_lines_dev': (_i, [_vp, _vp, _vp, _vp]),
+    'gpa_nan_trim_lims': (_i, [_vp, _vp, _vp]),
+    'gpa_nan_trim_lims_dev': (_i, [_vp, _vp, _vp]),
     'gpa_timer_start': (_i, [_vp]),
     'gpa_timer_stop': (_i, [_vp, _vp]),
     'gpa_set_profiling': (_i, [_vp, _i]),
@@ -531,6 +544,97 @@ class Plan:
         wxs, wys, thr = _f64(wxs).ravel(), _f64(wys).ravel(), _f64(thresholds).ravel()
         check(self.lib.gpa_wff_dev(self.handle, _ptr(int(image_ptr)), float(sigma), _ptr(wxs), len(wxs), _ptr(wys), len(wys),
                                    _ptr(thr), len(thr), float(scale), _ptr(int(out_ptr))), 'gpa_wff_dev')
+
+    # ---- image preparation (imagetools.py:92-194) ----------------------------------------------------------
+    def _mask(self, mask):
+        """a mask as a C-contiguous uint8 plane of 0 / 1, by truth value (0.5 and 256 are true)"""
+        mask = np.ascontiguousarray(np.asarray(mask) != 0, dtype=np.uint8)
+        if mask.shape != self.shape:
+            raise ValueError('mask shape %s does not match the plan %s' % (mask.shape, self.shape))
+        return mask
+
+    @staticmethod
+    def _nan_scale(nan_scale):
+        return (0, 0.0) if nan_scale is None else (1, float(nan_scale))
+
+    def gauss_homogenize(self, image, mask, sigma, nan_scale=None, want_vv=False):
+        """gpa_gauss_homogenize: image / VV with VV the masked Gaussian average; mask is taken by truth value.  Returns out,
+        or (out, VV) with want_vv"""
+        image, mask = self._img(image), self._mask(mask)
+        out = np.empty(self.shape, dtype=self.rdtype)
+        vv = np.empty(self.shape, dtype=self.rdtype) if want_vv else None
+        use, ns = self._nan_scale(nan_scale)
+        check(self.lib.gpa_gauss_homogenize(self.handle, _ptr(image), _ptr(mask), float(sigma), use, ns, _ptr(out), _ptr(vv)),
+              'gpa_gauss_homogenize')
+        return (out, vv) if want_vv else out
+
+    def gauss_homogenize_dev(self, image_ptr, mask_ptr, out_ptr, sigma, nan_scale=None, vv_ptr=None):
+        """gpa_gauss_homogenize_dev: image_ptr / out_ptr / vv_ptr (optional) -> n0 x n1 reals of the plan's precision, mask_ptr ->
+        n0 x n1 bytes, all on the device; out and vv overlap neither image nor mask; enqueued on the plan's stream"""
+        use, ns = self._nan_scale(nan_scale)
+        check(self.lib.gpa_gauss_homogenize_dev(self.handle, _ptr(int(image_ptr)), _ptr(int(mask_ptr)), float(sigma), use, ns,
+                                                _ptr(int(out_ptr)), None if vv_ptr is None else _ptr(int(vv_ptr))),
+              'gpa_gauss_homogenize_dev')
+
+    def mask_any_equal(self, frames, value, hit=None):
+        """gpa_mask_any_equal: hit | any(frames == value, axis=0) as a uint8 plane; frames (B, n0, n1), compared in the plan's
+        precision; hit: the plane of an earlier chunk, or None"""
+        frames = np.ascontiguousarray(frames, dtype=self.rdtype)
+        if frames.ndim != 3 or frames.shape[0] < 1 or frames.shape[1:] != self.shape:
+            raise ValueError('frames must be (B >= 1,) + %s, not %s' % (self.shape, frames.shape))
+        acc = hit is not None
+        hit = self._mask(hit).copy() if acc else np.empty(self.shape, dtype=np.uint8)
+        check(self.lib.gpa_mask_any_equal(self.handle, _ptr(frames), len(frames), float(value), int(acc), _ptr(hit)),
+              'gpa_mask_any_equal')
+        return hit
+
+    def mask_any_equal_dev(self, frames_ptr, B, value, hit_ptr, accumulate=False):
+        check(self.lib.gpa_mask_any_equal_dev(self.handle, _ptr(int(frames_ptr)), int(B), float(value), int(bool(accumulate)),
+                                              _ptr(int(hit_ptr))), 'gpa_mask_any_equal_dev')
+
+    def mask_erode_disk(self, mask, r, invert=False):
+        """gpa_mask_erode_disk: binary_erosion(~mask if invert else mask, disk(r)) as a uint8 plane"""
+        mask = self._mask(mask)
+        out = np.empty(self.shape, dtype=np.uint8)
+        check(self.lib.gpa_mask_erode_disk(self.handle, _ptr(mask), int(bool(invert)), int(r), _ptr(out)), 'gpa_mask_erode_disk')
+        return out
+
+    def mask_erode_disk_dev(self, in_ptr, out_ptr, r, invert=False):
+        check(self.lib.gpa_mask_erode_disk_dev(self.handle, _ptr(int(in_ptr)), int(bool(invert)), int(r), _ptr(int(out_ptr))),
+              'gpa_mask_erode_disk_dev')
+
+    def mask_bounds(self, mask):
+        """gpa_mask_bounds: int32 [first row, last row + 1, first column, last column + 1] holding a true sample"""
+        lims = np.empty(4, dtype=np.int32)
+        check(self.lib.gpa_mask_bounds(self.handle, _ptr(self._mask(mask)), _ptr(lims)), 'gpa_mask_bounds')
+        return lims
+
+    def mask_bounds_dev(self, mask_ptr):
+        lims = np.empty(4, dtype=np.int32)
+        check(self.lib.gpa_mask_bounds_dev(self.handle, _ptr(int(mask_ptr)), _ptr(lims)), 'gpa_mask_bounds_dev')
+        return lims
+
+    def nan_lines(self, image):
+        """gpa_nan_lines: (rows, cols) bool arrays, True where every sample of the line is NaN"""
+        rows, cols = np.empty(self.shape[0], dtype=np.uint8), np.empty(self.shape[1], dtype=np.uint8)
+        check(self.lib.gpa_nan_lines(self.handle, _ptr(self._img(image)), _ptr(rows), _ptr(cols)), 'gpa_nan_lines')
+        return rows.astype(bool), cols.astype(bool)
+
+    def nan_lines_dev(self, image_ptr):
+        rows, cols = np.empty(self.shape[0], dtype=np.uint8), np.empty(self.shape[1], dtype=np.uint8)
+        check(self.lib.gpa_nan_lines_dev(self.handle, _ptr(int(image_ptr)), _ptr(rows), _ptr(cols)), 'gpa_nan_lines_dev')
+        return rows.astype(bool), cols.astype(bool)
+
+    def nan_trim_lims(self, image):
+        """gpa_nan_trim_lims: int32 [x0, x1, y0, y1], the window the loop of trim_nans2 ends with"""
+        lims = np.empty(4, dtype=np.int32)
+        check(self.lib.gpa_nan_trim_lims(self.handle, _ptr(self._img(image)), _ptr(lims)), 'gpa_nan_trim_lims')
+        return lims
+
+    def nan_trim_lims_dev(self, image_ptr):
+        lims = np.empty(4, dtype=np.int32)
+        check(self.lib.gpa_nan_trim_lims_dev(self.handle, _ptr(int(image_ptr)), _ptr(lims)), 'gpa_nan_trim_lims_dev')
+        return lims
 
     @staticmethod
     def _rects(rects):

@@ -78,25 +78,7 @@ __global__ __launch_bounds__((GenGeom<T, LG>::THREADS)) void gf_rows_kernel(cons
   }
 }
 
-// columns: C complex transforms = 2C adjacent real columns per workgroup
-template <class T, int LG>
-struct GfColGeom {
-  using F = WgFFT<T, LG>;
-  static constexpr int cols() {
-    int c = 16;
-    while (c > 1 && (c * F::TPF > 1024 || (size_t)c * F::LDS_ELEMS * sizeof(cpx<T>) > 140 * 1024)) c /= 2;
-    return c;
-  }
-  static constexpr int C = cols();
-  static constexpr int NT = (sizeof(T) == 4 && C >= 2) ? 2 : 1;   // complex transforms per thread
-  static constexpr int CT = C / NT;
-  static constexpr int REGION = CT * F::LDS_ELEMS;
-  static constexpr int THREADS = CT * F::TPF;
-  static constexpr size_t LDS_BYTES = (size_t)NT * REGION * sizeof(cpx<T>);
-  static constexpr bool FITS = (size_t)F::LDS_ELEMS * sizeof(cpx<T>) <= 140 * 1024;
-  static constexpr int RC = 2 * C;   // real columns per workgroup
-};
-
+// columns: tiles of GfColGeom (gpa_gaussfft.h)
 template <class T, int LG>
 __global__ __launch_bounds__((GfColGeom<T, LG>::THREADS)) void gf_cols_kernel(const T* __restrict__ in, T* __restrict__ out, int n0,
                                                                             int n1, int R, const T* __restrict__ H,

@@ -366,4 +366,33 @@ hipError_t ucell_expand(int dtype, const double* d_cell, const UcellGeom& g, dou
 hipError_t wff_run(int dtype, const void* d_img, int n0, int n1, int s, const void* d_txr, int Kx, const void* d_tyr, int Ky,
                    const void* d_thr2, int T, double scale, void* d_A, void* d_B, void* d_out, hipStream_t st);
 
+// ---- image preparation (gpa_prep.hip; geometry and limits: gpa_prep.h) ---------------------------------------------------
+// one masked homogenisation: image / out / vv (nullable) n0 x n1 of dtype, mask n0 x n1 bytes; num, den: two planes of dtype
+// and cov0, cov: two byte planes of scratch; mm: two 64-bit words.  lg0 && lg1: the FFT route with the tables H / tw of the
+// two axes (gaussfft_table, twiddles of 2^lg), else the direct route with the 2R + 1 taps w (doubles).  Enqueued on s.
+struct PrepHomogenize {
+  const void* image;
+  const uint8_t* mask;
+  void *num, *den;
+  uint8_t *cov0, *cov;
+  unsigned long long* mm;
+  void *out, *vv;
+  int n0, n1, R, lg0, lg1;
+  const void *H0, *tw0, *H1, *tw1;
+  const double* w;
+  int use_nan_scale;
+  double nan_scale;
+};
+hipError_t prep_homogenize(int dtype, const PrepHomogenize& a, hipStream_t s);
+// hit = [hit |] any_b(frames[b] == value), compared in dtype
+hipError_t prep_any_equal(int dtype, const void* frames, int B, int n0, int n1, double value, int accumulate, uint8_t* hit,
+                          hipStream_t s);
+// out = binary_erosion(invert ? !in : in, disk(r)); hd: one byte plane of scratch, chord: 2r + 1 bytes (prep_disk_chord)
+hipError_t prep_erode_disk(const uint8_t* in, int invert, int r, int n0, int n1, uint8_t* hd, const uint8_t* chord, uint8_t* out,
+                           hipStream_t s);
+// lims (device, 4 ints): first / last + 1 row and column with a true sample; {n0, 0, n1, 0} for an all-false mask
+hipError_t prep_mask_bounds(const uint8_t* mask, int n0, int n1, int* lims, hipStream_t s);
+hipError_t prep_nan_lines(int dtype, const void* image, int n0, int n1, uint8_t* rows, uint8_t* cols, hipStream_t s);
+hipError_t prep_trim_lims(int dtype, const void* image, int n0, int n1, int* lims, hipStream_t s);
+
 }  // namespace gpa

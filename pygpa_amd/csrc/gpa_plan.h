@@ -225,6 +225,12 @@ struct gpa_plan {
   // windowed Fourier filtering (gpa_api_wff.hip), grown on demand: tap tables, the A plane and the T planes B of a call;
   // device staging of the host-pointer form (image, T output planes)
   DevBuf wff{&ws_bytes}, wff_stage{&ws_bytes};
+  // image preparation (gpa_api_prep.hip), grown on demand: the num / den planes, two byte planes, the chords and the small
+  // words of a call; the filter tables of the last (sigma, segment lengths); device staging of the host-pointer forms
+  DevBuf prep{&ws_bytes}, prep_tab{&ws_bytes}, prep_stage{&ws_bytes};
+  double prep_sigma = -1.0;       // what prep_tab holds: sigma, the two transform lengths (0, 0: the direct route's taps)
+  int prep_lg0 = -1, prep_lg1 = -1;
+  int prep_chord_r = -1;          // the radius whose chords sit in prep
   // a8 iterate_GPA (gpa_api_iterate.hip), grown on demand: the Huber work of the batched plane fit, behind it the driver's
   // amax / psi / weight planes (and the prs / w planes of its host form)
   DevBuf d_iter{&ws_bytes};
