@@ -570,6 +570,37 @@ int gpa_nan_lines_dev(gpa_plan* plan, const void* image_dev, uint8_t* rows, uint
 int gpa_nan_trim_lims(gpa_plan* plan, const void* image, int32_t* lims);
 int gpa_nan_trim_lims_dev(gpa_plan* plan, const void* image_dev, int32_t* lims);
 
+/* ---- per-line medians and homogenize_per_axis (pyGPA/imagetools.py:112-125) ------------------------------------------------
+ * out = the median of every line of the plan's n0 x n1 image along `axis`: axis 0 gives the n1 column medians, axis 1 the n0
+ * row medians, in the plan's precision and with NumPy's bits (the median is selected, not approximated: the middle sample,
+ * or (a + b) / 2 of the two middle ones).  mask (nullable, n0 x n1 bytes, 0 is false) leaves samples out, as NaN samples are
+ * left out: np.nanmedian(where(mask, image, nan), axis); a line without any sample gives NaN.  propagate_nan != 0 gives
+ * np.median instead: a NaN or masked sample makes the median of its line NaN.  A line holds at most GPA_LINES_MAX_N samples
+ * (its keys stay in LDS): GPA_ERR_ARG beyond; the other axis is only bound by the plan.                                   */
+#define GPA_LINES_MAX_N 16384
+int gpa_line_nanmedian(gpa_plan* plan, const void* image, const uint8_t* mask, int axis, int propagate_nan, void* out);
+int gpa_line_nanmedian_dev(gpa_plan* plan, const void* image_dev, const uint8_t* mask_dev, int axis, int propagate_nan, void* out_dev);
+/* homogenize_per_axis of nb frames (nb x n0 x n1, one mask for all, nullable) with reducfunc = np.nanmedian (propagate_nan = 0)
+ * or np.median (1):  for axis 0, then axis 1:  profile = gaussian_filter(median of where(mask, res, nan) along the axis, sigma),
+ * res /= profile / max(profile).  The medians of axis 1 are those of the image after the division of axis 0, which is applied
+ * as the rows are loaded; the image is written once, out = (image / q0[column]) / q1[row].  The filter runs along the line
+ * only (along the unit axis the reference's second pass multiplies by the taps' sum), as a direct f64 sum over the 'reflect'
+ * extension, rounded once.  max propagates NaN as np.max does: one line without a sample turns the whole frame NaN, as in the
+ * reference.  profiles (nullable) receives per frame the n1 values of the axis-0 profile, then the n0 values of the axis-1
+ * profile.  Both axes <= GPA_LINES_MAX_N, sigma <= 16384, 1 <= nb <= 65535: GPA_ERR_ARG otherwise.  out may be image in the
+ * _dev form.                                                                                                             */
+int gpa_homogenize_per_axis(gpa_plan* plan, const void* image, const uint8_t* mask, double sigma, int propagate_nan, int nb,
+                            void* out, void* profiles);
+int gpa_homogenize_per_axis_dev(gpa_plan* plan, const void* image_dev, const uint8_t* mask_dev, double sigma, int propagate_nan,
+                                int nb, void* out_dev, void* profiles_dev);
+/* The same filter and divisions for one frame whose REDUCED lines the caller computed (any reducfunc): line0 = the n1 values
+ * reduced along axis 0, line1 = the n0 values reduced along axis 1 of the image after axis 0.  line1 null: out = image / q0,
+ * the image after axis 0, from which the caller reduces line1.  profiles (nullable): n1 values, then n0 when line1 is given. */
+int gpa_homogenize_lines(gpa_plan* plan, const void* image, double sigma, const void* line0, const void* line1, void* out,
+                         void* profiles);
+int gpa_homogenize_lines_dev(gpa_plan* plan, const void* image_dev, double sigma, const void* line0_dev, const void* line1_dev,
+                             void* out_dev, void* profiles_dev);
+
 /* timing hooks used by bench.py: elapsed milliseconds between two recorded
  * events on the plan's stream (HIP events, so it measures the stream the
  * kernels are launched on).                                                   */

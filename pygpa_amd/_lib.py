@@ -19,6 +19,7 @@ UCELL_MAX_FRAMES = 65535     # frames of one gpa_unit_cell_average_batch_dev cal
 UNDISTORT_MAX_FRAMES = 65535     # frames of one gpa_undistort_image_batch[_dev] call
 WFF_MAX_S, WFF_MAX_T = 40, 8     # half-window round(2 sigma) and thresholds of one gpa_wff[_dev] call
 PREP_MAX_R, PREP_MAX_N1 = 254, 32768     # erosion radius of gpa_mask_erode_disk, row length of gpa_gauss_homogenize
+LINES_MAX_N = 16384                      # longest line of gpa_line_nanmedian / gpa_homogenize_per_axis (GPA_LINES_MAX_N)
 _DTYPES = {GPA_F32: (np.float32, np.complex64), GPA_F64: (np.float64, np.complex128)}
 
 # every symbol of include/gpa_hip.h: name -> (restype, argtypes)
@@ -120,6 +121,12 @@ SIGNATURES = {
     'gpa_nan_lines_dev': (_i, [_vp, _vp, _vp, _vp]),
     'gpa_nan_trim_lims': (_i, [_vp, _vp, _vp]),
     'gpa_nan_trim_lims_dev': (_i, [_vp, _vp, _vp]),
+    'gpa_line_nanmedian': (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    'gpa_line_nanmedian_dev': (_i, [_vp, _vp, _vp, _i, _i, _vp]),
+    'gpa_homogenize_per_axis': (_i, [_vp, _vp, _vp, _d, _i, _i, _vp, _vp]),
+    'gpa_homogenize_per_axis_dev': (_i, [_vp, _vp, _vp, _d, _i, _i, _vp, _vp]),
+    'gpa_homogenize_lines': (_i, [_vp, _vp, _d, _vp, _vp, _vp, _vp]),
+    'gpa_homogenize_lines_dev': (_i, [_vp, _vp, _d, _vp, _vp, _vp, _vp]),
     'gpa_timer_start': (_i, [_vp]),
     'gpa_timer_stop': (_i, [_vp, _vp]),
     'gpa_set_profiling': (_i, [_vp, _i]),
@@ -635,6 +642,74 @@ class Plan:
         lims = np.empty(4, dtype=np.int32)
         check(self.lib.gpa_nan_trim_lims_dev(self.handle, _ptr(int(image_ptr)), _ptr(lims)), 'gpa_nan_trim_lims_dev')
         return lims
+
+    # ---- per-line medians, homogenize_per_axis (imagetools.py:112-125) -------------------------------------
+    def _mask_or_none(self, mask):
+        return None if mask is None else self._mask(mask)
+
+    def line_nanmedian(self, image, axis, mask=None, propagate_nan=False):
+        """gpa_line_nanmedian: np.nanmedian(where(mask, image, nan), axis) (np.median with propagate_nan) as a 1-D array of
+        the plan's precision: n1 column medians for axis 0, n0 row medians for axis 1"""
+        image, mask = self._img(image), self._mask_or_none(mask)
+        out = np.empty(self.shape[1 - int(axis)] if int(axis) in (0, 1) else 1, dtype=self.rdtype)
+        check(self.lib.gpa_line_nanmedian(self.handle, _ptr(image), _ptr(mask), int(axis), int(bool(propagate_nan)), _ptr(out)),
+              'gpa_line_nanmedian')
+        return out
+
+    def line_nanmedian_dev(self, image_ptr, mask_ptr, axis, out_ptr, propagate_nan=False):
+        """gpa_line_nanmedian_dev: device pointers (mask_ptr may be None); enqueued on the plan's stream"""
+        check(self.lib.gpa_line_nanmedian_dev(self.handle, _ptr(int(image_ptr)), None if mask_ptr is None else _ptr(int(mask_ptr)),
+                                              int(axis), int(bool(propagate_nan)), _ptr(int(out_ptr))), 'gpa_line_nanmedian_dev')
+
+    def homogenize_per_axis(self, frames, sigma, mask=None, propagate_nan=False, want_profiles=False):
+        """gpa_homogenize_per_axis of one image (n0, n1) or a stack (B, n0, n1) sharing `mask`, in one device call.  Returns out,
+        or (out, profile0, profile1) with want_profiles: the filtered profiles along axis 0 ((B,) n1 values) and axis 1 ((B,) n0)"""
+        frames = np.ascontiguousarray(frames, dtype=self.rdtype)
+        single = frames.ndim == 2
+        if frames.ndim not in (2, 3) or frames.shape[-2:] != self.shape or frames.shape[0] < 1:
+            raise ValueError('frames %s do not match the plan %s' % (frames.shape, self.shape))
+        nb = 1 if single else frames.shape[0]
+        mask = self._mask_or_none(mask)
+        out = np.empty(frames.shape, dtype=self.rdtype)
+        prof = np.empty((nb, self.shape[1] + self.shape[0]), dtype=self.rdtype) if want_profiles else None
+        check(self.lib.gpa_homogenize_per_axis(self.handle, _ptr(frames), _ptr(mask), float(sigma), int(bool(propagate_nan)), nb,
+                                               _ptr(out), _ptr(prof)), 'gpa_homogenize_per_axis')
+        if not want_profiles:
+            return out
+        p0, p1 = prof[:, :self.shape[1]].copy(), prof[:, self.shape[1]:].copy()
+        return (out, p0[0], p1[0]) if single else (out, p0, p1)
+
+    def homogenize_per_axis_dev(self, image_ptr, mask_ptr, out_ptr, sigma, propagate_nan=False, nb=1, profiles_ptr=None):
+        """gpa_homogenize_per_axis_dev: image_ptr / out_ptr -> nb x n0 x n1 reals of the plan's precision, mask_ptr (or None) ->
+        n0 x n1 bytes, profiles_ptr (or None) -> nb x (n1 + n0) reals, all on the device; enqueued on the plan's stream"""
+        check(self.lib.gpa_homogenize_per_axis_dev(self.handle, _ptr(int(image_ptr)), None if mask_ptr is None else _ptr(int(mask_ptr)),
+                                                   float(sigma), int(bool(propagate_nan)), int(nb), _ptr(int(out_ptr)),
+                                                   None if profiles_ptr is None else _ptr(int(profiles_ptr))),
+              'gpa_homogenize_per_axis_dev')
+
+    def homogenize_lines(self, image, sigma, line0, line1=None, want_profiles=False):
+        """gpa_homogenize_lines: the filter and the divisions of homogenize_per_axis with the reduced lines given (line0: n1
+        values, line1: n0 values or None for the image after axis 0 alone)"""
+        image = self._img(image)
+        line0 = np.ascontiguousarray(line0, dtype=self.rdtype).ravel()
+        if line0.size != self.shape[1]:
+            raise ValueError('line0 needs %d values' % self.shape[1])
+        if line1 is not None:
+            line1 = np.ascontiguousarray(line1, dtype=self.rdtype).ravel()
+            if line1.size != self.shape[0]:
+                raise ValueError('line1 needs %d values' % self.shape[0])
+        out = np.empty(self.shape, dtype=self.rdtype)
+        prof = np.empty(self.shape[1] + (0 if line1 is None else self.shape[0]), dtype=self.rdtype) if want_profiles else None
+        check(self.lib.gpa_homogenize_lines(self.handle, _ptr(image), float(sigma), _ptr(line0), _ptr(line1), _ptr(out), _ptr(prof)),
+              'gpa_homogenize_lines')
+        if not want_profiles:
+            return out
+        return out, prof[:self.shape[1]].copy(), (None if line1 is None else prof[self.shape[1]:].copy())
+
+    def homogenize_lines_dev(self, image_ptr, sigma, line0_ptr, line1_ptr, out_ptr, profiles_ptr=None):
+        check(self.lib.gpa_homogenize_lines_dev(self.handle, _ptr(int(image_ptr)), float(sigma), _ptr(int(line0_ptr)),
+                                                None if line1_ptr is None else _ptr(int(line1_ptr)), _ptr(int(out_ptr)),
+                                                None if profiles_ptr is None else _ptr(int(profiles_ptr))), 'gpa_homogenize_lines_dev')
 
     @staticmethod
     def _rects(rects):

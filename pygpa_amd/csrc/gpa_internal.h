@@ -395,4 +395,18 @@ hipError_t prep_mask_bounds(const uint8_t* mask, int n0, int n1, int* lims, hipS
 hipError_t prep_nan_lines(int dtype, const void* image, int n0, int n1, uint8_t* rows, uint8_t* cols, hipStream_t s);
 hipError_t prep_trim_lims(int dtype, const void* image, int n0, int n1, int* lims, hipStream_t s);
 
+// ---- per-line medians and homogenize_per_axis (gpa_lines.hip; keys, ranks, limits: gpa_lines.h) -------------------------------
+// med[f * med_stride + l] = median of line l of frame f (nb frames of n0 x n1, dtype): axis 0 the n1 column medians (through
+// the transpose into tws, nb planes of scratch), axis 1 the n0 row medians.  mask (nullable): n0 x n1 bytes shared by the frames,
+// a false sample is left out.  q (nullable, axis 1 only): per frame n1 divisors applied as the line is loaded.  propagate: a
+// left-out or NaN sample makes the median NaN.  hipErrorInvalidValue for a line longer than LINES_MAX_N.  Enqueued on s.
+hipError_t lines_median(int dtype, const void* image, const uint8_t* mask, int n0, int n1, int nb, int axis, int propagate,
+                        const void* q, size_t q_stride, void* tws, void* med, size_t med_stride, hipStream_t s);
+// prof = gaussian_filter(line) under 'reflect' with the 2R + 1 taps w (doubles), q = prof / max(prof); nb lines `stride` apart
+hipError_t lines_profile(int dtype, const void* line, size_t stride, int n, int nb, const double* w, int R, void* prof, void* q,
+                         hipStream_t s);
+// out = (image / q0[column]) / q1[row]; q1 null: the first division only
+hipError_t lines_apply(int dtype, const void* image, const void* q0, size_t q0_stride, const void* q1, size_t q1_stride, void* out,
+                       int n0, int n1, int nb, hipStream_t s);
+
 }  // namespace gpa

@@ -231,6 +231,10 @@ struct gpa_plan {
   double prep_sigma = -1.0;       // what prep_tab holds: sigma, the two transform lengths (0, 0: the direct route's taps)
   int prep_lg0 = -1, prep_lg1 = -1;
   int prep_chord_r = -1;          // the radius whose chords sit in prep
+  // per-line medians and homogenize_per_axis (gpa_api_lines.hip), grown on demand: the transposed planes and the median /
+  // profile / divisor lines of a call; the taps of the last sigma; device staging of the host-pointer forms
+  DevBuf lines{&ws_bytes}, lines_tab{&ws_bytes}, lines_stage{&ws_bytes};
+  double lines_sigma = -1.0;      // the sigma whose taps sit in lines_tab
   // a8 iterate_GPA (gpa_api_iterate.hip), grown on demand: the Huber work of the batched plane fit, behind it the driver's
   // amax / psi / weight planes (and the prs / w planes of its host form)
   DevBuf d_iter{&ws_bytes};

@@ -4,8 +4,10 @@ Same names, positional order and defaults as the reference, plus the house ``dty
 outputs are host NumPy arrays; the work runs in libgpa_hip.so and there is no CPU fallback.  The ``*_dev`` forms take a
 ``_lib.Plan`` and device pointers for callers that keep the image on the device between stages (undistort -> trim ...).
 
-Not mirrored: ``homogenize_per_axis`` (its reducfunc is an arbitrary callable, a per-line median by default: a selection kernel
-of its own), the plotting helpers (``fftplot``, ``indicate_k``) and ``to_KovesiRGB``.
+``homogenize_per_axis`` runs its default reducfunc, the per-line ``np.nanmedian`` (and ``np.median``), as a selection kernel on
+the device; any other callable is evaluated on the host and only its lines go to the device.
+
+Not mirrored: the plotting helpers (``fftplot``, ``indicate_k``) and ``to_KovesiRGB``.
 """
 import numpy as np
 
@@ -85,6 +87,123 @@ def gauss_homogenize_dev(plan, image_ptr, mask_ptr, out_ptr, sigma, nan_scale=No
     if not np.isfinite(sigma) or sigma <= 0:
         raise ValueError('sigma must be positive and finite')
     plan.gauss_homogenize_dev(image_ptr, mask_ptr, out_ptr, sigma, nan_scale, vv_ptr)
+
+
+# frames of one device call of homogenize_per_axis_stack: chunks of at most this many bytes (one frame at least)
+AXIS_CHUNK_BYTES = 256 << 20
+
+
+def _per_axis_args(image, mask, sigma, what='image', ndim=2):
+    image = np.asarray(image)
+    if image.ndim != ndim:
+        raise ValueError('%s must be %d-D' % (what, ndim))
+    if image.dtype.kind not in 'fiub':
+        raise TypeError('%s must be real' % what)
+    if mask is not None:
+        mask = np.asarray(mask)
+        if mask.dtype != np.bool_:
+            raise TypeError('mask must have dtype bool')
+        if mask.shape != image.shape[-2:]:
+            raise ValueError('mask %s does not match the image %s' % (mask.shape, image.shape[-2:]))
+    if np.ndim(sigma) != 0:
+        raise ValueError('sigma must be one scalar')
+    sigma = float(sigma)
+    if not np.isfinite(sigma) or sigma <= 0:
+        raise ValueError('sigma must be positive and finite')
+    if min(image.shape[-2:]) < 4 or max(image.shape[-2:]) > _lib.LINES_MAX_N:
+        raise ValueError('both axes must hold 4 .. %d samples, not %s' % (_lib.LINES_MAX_N, image.shape[-2:]))
+    return image, mask, sigma
+
+
+def homogenize_per_axis(image, sigma=200, mask=None, reducfunc=np.nanmedian, dtype=None):
+    """Divide out a smooth profile per column, then per row (imagetools.py:112-125): for axis 0, then axis 1,
+    profile = gaussian_filter(reducfunc(where(mask, res, nan), axis, keepdims=True), sigma); res /= profile / profile.max().
+    Removes detector stripes and per-line gain, which a 2-D Gaussian average follows instead.
+
+    reducfunc np.nanmedian (the default) and np.median are recognised by identity and run on the device: exact per-line
+    selections with NumPy's bits, the second axis taken from the image after the first division without storing it.  Any
+    other callable is called on the host exactly as the reference calls it, once per axis; its line goes to the device for
+    the filter and the divisions.  That path costs a download of res per axis.
+    A line without any valid sample has the median NaN, and max() spreads it: the whole result is NaN, as in the reference.
+
+    image: 2-D real, both axes 4 .. 16384; mask: None or 2-D bool of the same shape; sigma: one positive finite scalar.
+    Deviation: an integer image is converted to the plan's precision first (the reference fails on its in-place division)."""
+    image, mask, sigma = _per_axis_args(image, mask, sigma)
+    if not callable(reducfunc):
+        raise TypeError('reducfunc must be callable')
+    plan = _lib.get_plan(image.shape, 1, _real(dtype))
+    if reducfunc is np.nanmedian or reducfunc is np.median:
+        return plan.homogenize_per_axis(image, sigma, mask, propagate_nan=reducfunc is np.median)
+    image = plan._img(image)
+    line0 = _reduced(reducfunc, image, mask, 0)
+    res = plan.homogenize_lines(image, sigma, line0)
+    return plan.homogenize_lines(image, sigma, line0, _reduced(reducfunc, res, mask, 1))
+
+
+def _reduced(reducfunc, res, mask, axis):
+    src = res if mask is None else np.where(mask, res, np.nan)
+    line = np.asarray(reducfunc(src, axis=axis, keepdims=True))
+    want = (1, res.shape[1]) if axis == 0 else (res.shape[0], 1)
+    if line.shape != want:
+        raise ValueError('reducfunc returned the shape %s along axis %d, not %s' % (line.shape, axis, want))
+    return line
+
+
+def homogenize_per_axis_stack(frames, sigma=200, mask=None, dtype=None):
+    """homogenize_per_axis (np.nanmedian) of every frame of a stack (B, n0, n1) that shares one mask: one device call per
+    chunk of frames.  Frame b equals the single call bit for bit."""
+    frames, mask, sigma = _per_axis_args(frames, mask, sigma, what='frames', ndim=3)
+    if frames.shape[0] < 1:
+        raise ValueError('frames must hold at least one frame')
+    real = _real(dtype)
+    plan = _lib.get_plan(frames.shape[1:], 1, real)
+    per = max(1, AXIS_CHUNK_BYTES // max(1, frames.shape[1] * frames.shape[2] * np.dtype(real).itemsize))
+    out = np.empty(frames.shape, dtype=real)
+    for a in range(0, len(frames), per):
+        out[a:a + per] = plan.homogenize_per_axis(frames[a:a + per], sigma, mask)
+    return out
+
+
+def homogenize_per_axis_dev(plan, image_ptr, mask_ptr, out_ptr, sigma, profiles_ptr=None):
+    """homogenize_per_axis (np.nanmedian) of an image that is resident on the device (`plan`: a _lib.Plan of its shape;
+    image_ptr / out_ptr: device pointers to n0 x n1 reals of the plan's precision; mask_ptr: n0 x n1 bytes, 0 is false, or
+    None): enqueued on the plan's stream, nothing comes to the host.  profiles_ptr (optional) receives the two filtered
+    profiles, n1 values then n0."""
+    sigma = float(sigma)
+    if not np.isfinite(sigma) or sigma <= 0:
+        raise ValueError('sigma must be positive and finite')
+    plan.homogenize_per_axis_dev(image_ptr, mask_ptr, out_ptr, sigma, profiles_ptr=profiles_ptr)
+
+
+def nanmedian_lines(image, axis, mask=None, keepdims=True, dtype=None):
+    """np.nanmedian(where(mask, image, nan), axis=axis, keepdims=keepdims) on the device: an exact selection per line, NumPy's
+    bits in both precisions.  image: 2-D real; axis 0 or 1 (the reduced axis holds at most 16384 samples); mask: None or 2-D
+    bool.  An axis shorter than the plan's smallest (4) is served by repeating the image four times along it, which leaves
+    every median as it is: each sample then occurs four times, and the two middle ranks hold what they held."""
+    image = _image2d(image)
+    if axis not in (0, 1, -1, -2):
+        raise ValueError('axis must be 0 or 1')
+    axis = axis % 2
+    if mask is not None:
+        mask = np.asarray(mask)
+        if mask.dtype != np.bool_:
+            raise TypeError('mask must have dtype bool')
+        if mask.shape != image.shape:
+            raise ValueError('mask %s does not match the image %s' % (mask.shape, image.shape))
+    if image.shape[0] < 1 or image.shape[1] < 1:
+        raise ValueError('image is empty')
+    if image.shape[axis] > _lib.LINES_MAX_N:
+        raise ValueError('axis %d holds %d samples, more than %d' % (axis, image.shape[axis], _lib.LINES_MAX_N))
+    real = _real(dtype)
+    nlines = image.shape[1 - axis]
+    reps = tuple(4 if n < 4 else 1 for n in image.shape)
+    if reps != (1, 1):
+        image = np.tile(image, reps)
+        mask = None if mask is None else np.tile(mask, reps)
+    med = _lib.get_plan(image.shape, 1, real).line_nanmedian(image, axis, mask)[:nlines]
+    if not keepdims:
+        return med
+    return med.reshape((1, nlines) if axis == 0 else (nlines, 1))
 
 
 def generate_mask(dataset, mask_value, r=20, dtype=None):
