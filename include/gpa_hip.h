@@ -382,6 +382,30 @@ int gpa_props_from_jac_dev(int device, int dtype, size_t npx, const void* jac, i
                            double refangle, double refscale, int diff, void* props,
                            void* stream);
 
+/* Per-pixel Kerelsky fits -- twist theta, strain direction psi, heterostrain eps and lattice angle xi (degrees, eps a ratio)
+ * from the displacement-gradient field; replaces Kerelsky_J's per-pixel least squares (property_extract.py:780-883) and, with
+ * npx = 1, its global fit and Kerelsky_Jac's (:707-777).  Per pixel, with W(a) the rotation by a, D(e) = diag(1/(1+e),
+ * 1/(1-0.16 e)) and V = W(psi), it minimises |1000 vec(V^T D V W(theta+xi) - W(xi) - A)|^2 / 2 over theta >= 0, eps >= 0 by a
+ * bounded Levenberg-Marquardt iteration with the analytic Jacobian, in f64 whatever the dtype (csrc/gpa_kerelsky.h).
+ *   jac   npx x 2 x 2 in the dtype: J when a0 is given, and then A = a0 + a0 J is formed per pixel; A itself when a0 is NULL
+ *   a0    4 doubles (2 x 2, row-major) or NULL
+ *   x0    the start (theta, psi, eps, xi), theta >= 0 and eps >= 0
+ *   max_nfev    trial evaluations per start, >= 1 (the reference's default: 50)
+ *   retry_cost  further starts -- psi + 90 degrees, then the closed-form root where one exists -- are tried while the best
+ *               cost exceeds this (the reference: 1e-5 per pixel, 1e-20 in the global fits); the best result is kept
+ *   out   npx x 4 in the dtype: theta, psi (the representative within 90 degrees of x0's), eps, xi (within 180 of x0's);
+ *         theta >= 0 and eps >= 0 exactly
+ *   cost  npx doubles, the cost at out before rounding to the dtype; may be NULL
+ * A pixel whose A is not finite gives four NaNs and a NaN cost (the reference raises there).  Needs no plan.  Argument errors
+ * (GPA_ERR_ARG) name the argument and come before any device is touched.  _dev: device pointers (a0 and x0 stay host
+ * pointers), asynchronous on the given hipStream_t.                                                                       */
+#define GPA_KERELSKY_MAX_NPX 0x1000000000ull
+int gpa_kerelsky_fit(int device, int dtype, size_t npx, const void* jac, const double* a0,
+                     const double* x0, int max_nfev, double retry_cost, void* out, double* cost);
+int gpa_kerelsky_fit_dev(int device, int dtype, size_t npx, const void* jac, const double* a0,
+                         const double* x0, int max_nfev, double retry_cost, void* out, double* cost,
+                         void* stream);
+
 /* f-4 -- robust plane fit a0*x + a1*y + a2 (x = row, y = column index) through an n0 x n1 map:
  * the minimiser of the Huber cost that fit_plane (mathtools.py:30-47, scipy least_squares with
  * loss='huber', f_scale 1, start at 0) approaches, by iteratively reweighted least squares with the

@@ -88,6 +88,8 @@ SIGNATURES = {
     'gpa_lockin_weights_dev': (_i, [_vp, _vp, _i, _vp]),
     'gpa_props_from_jac': (_i, [_i, _i, _sz, _vp, _i, _d, _d, _i, _vp]),
     'gpa_props_from_jac_dev': (_i, [_i, _i, _sz, _vp, _i, _d, _d, _i, _vp, _vp]),
+    'gpa_kerelsky_fit': (_i, [_i, _i, _sz, _vp, _vp, _vp, _i, _d, _vp, _vp]),
+    'gpa_kerelsky_fit_dev': (_i, [_i, _i, _sz, _vp, _vp, _vp, _i, _d, _vp, _vp, _vp]),
     'gpa_fit_plane': (_i, [_vp, _vp, _i, _d, _dp, _ip]),
     'gpa_fit_plane_dev': (_i, [_vp, _vp, _i, _d, _dp, _ip]),
     'gpa_fit_planes_dev': (_i, [_vp, _vp, _i, _i, _d, _vp, _vp]),
@@ -1405,6 +1407,54 @@ def props_from_jac(jac, add_identity=False, refangle=0., refscale=1., diff=False
                                     int(bool(add_identity)), float(refangle), float(refscale), int(bool(diff)),
                                     _ptr(props)), 'gpa_props_from_jac')
     return props
+
+
+def _kerelsky_args(x0, a0, max_nfev, retry_cost, dtype):
+    """the checked scalar arguments of gpa_kerelsky_fit[_dev]: (dtype code, x0, a0 or None, max_nfev, retry_cost)"""
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError('dtype must be float32 or float64')
+    x0 = np.ascontiguousarray(x0, dtype=np.float64)
+    if x0.shape != (4,) or not np.isfinite(x0).all():
+        raise ValueError('x0 must be four finite numbers (theta, psi, epsilon, xi)')
+    if x0[0] < 0 or x0[2] < 0:
+        raise ValueError('x0 must respect the bounds theta >= 0 and epsilon >= 0')
+    if a0 is not None:
+        a0 = np.ascontiguousarray(a0, dtype=np.float64)
+        if a0.shape != (2, 2) or not np.isfinite(a0).all():
+            raise ValueError('a0 must be a finite 2 x 2 matrix')
+    if int(max_nfev) != max_nfev or int(max_nfev) < 1:
+        raise ValueError('max_nfev must be an integer >= 1')
+    if np.isnan(retry_cost):
+        raise ValueError('retry_cost must not be NaN')
+    return GPA_F32 if dtype == np.float32 else GPA_F64, x0, a0, int(max_nfev), float(retry_cost)
+
+
+def kerelsky_fit(jac, x0, a0=None, max_nfev=50, retry_cost=1e-5, dtype=np.float64, device=0):
+    """Plan-free per-pixel Kerelsky fits (gpa_kerelsky_fit): jac (..., 2, 2) -- J when a0 (2 x 2) is given, else A itself -- and
+    the start x0 -> (X (..., 4) in the dtype, cost (...) in f64)."""
+    code, x0, a0, max_nfev, retry_cost = _kerelsky_args(x0, a0, max_nfev, retry_cost, dtype)
+    jac = np.ascontiguousarray(jac, dtype=dtype)
+    if jac.shape[-2:] != (2, 2):
+        raise ValueError('jac must have shape (..., 2, 2)')
+    lead = jac.shape[:-2]
+    out = np.empty(lead + (4,), dtype=dtype)
+    cost = np.empty(lead, dtype=np.float64)
+    check(load().gpa_kerelsky_fit(int(device), code, jac.size // 4, _ptr(jac), None if a0 is None else _ptr(a0), _ptr(x0), max_nfev,
+                                  retry_cost, _ptr(out), _ptr(cost)), 'gpa_kerelsky_fit')
+    return out, cost
+
+
+def kerelsky_fit_dev(jac_ptr, npx, x0, out_ptr, a0=None, max_nfev=50, retry_cost=1e-5, cost_ptr=None, dtype=np.float64, device=0,
+                     stream=None):
+    """gpa_kerelsky_fit_dev: device pointers jac (npx x 2 x 2) and out (npx x 4) in the dtype, cost (npx doubles, optional);
+    asynchronous on `stream` (a hipStream_t as an integer; None: the default stream)."""
+    code, x0, a0, max_nfev, retry_cost = _kerelsky_args(x0, a0, max_nfev, retry_cost, dtype)
+    if int(npx) < 0:
+        raise ValueError('npx must be >= 0')
+    check(load().gpa_kerelsky_fit_dev(int(device), code, int(npx), _ptr(int(jac_ptr)), None if a0 is None else _ptr(a0), _ptr(x0),
+                                      max_nfev, retry_cost, _ptr(int(out_ptr)), None if cost_ptr is None else _ptr(int(cost_ptr)),
+                                      None if stream is None else _ptr(int(stream))), 'gpa_kerelsky_fit_dev')
 
 
 @atexit.register

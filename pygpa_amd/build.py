@@ -20,7 +20,7 @@ LIB = os.path.join(HERE, 'libgpa_hip.so')
 SOURCES = ['gpa_sweep.hip', 'gpa_passb_shared.hip', 'gpa_sweep_ext.hip', 'gpa_reconstruct.hip', 'gpa_unwrap.hip', 'gpa_unwrap_rows.hip', 'gpa_unwrap_rowhalf.hip', 'gpa_unwrap_pqdct.hip', 'gpa_unwrap_rowpers.hip', 'gpa_unwrap_rowhalfpers.hip', 'gpa_unwrap_cols.hip', 'gpa_unwrap_colhalf.hip', 'gpa_unwrap_colstream.hip', 'gpa_unwrap_stencil.hip', 'gpa_unwrap_generic.hip',
            'gpa_unwrap_tables.hip', 'gpa_dft2.hip', 'gpa_gaussfft.hip', 'gpa_warp.hip', 'gpa_tiles.hip', 'gpa_peaks.hip', 'gpa_api.hip', 'gpa_api_tables.hip', 'gpa_api_sweep.hip', 'gpa_api_unwrap.hip', 'gpa_api_driver.hip',
            'gpa_api_tiles.hip', 'gpa_api_warp.hip', 'gpa_api_spectral.hip', 'gpa_ucell.hip', 'gpa_api_ucell.hip', 'gpa_iterate.hip', 'gpa_api_iterate.hip', 'gpa_wff.hip', 'gpa_api_wff.hip',
-           'gpa_prep.hip', 'gpa_api_prep.hip', 'gpa_lines.hip', 'gpa_api_lines.hip']
+           'gpa_prep.hip', 'gpa_api_prep.hip', 'gpa_lines.hip', 'gpa_api_lines.hip', 'gpa_kerelsky.hip', 'gpa_api_kerelsky.hip']
 ARCH = 'gfx950'
 # -fvisibility=hidden: the dynamic symbol table is the C ABI of include/gpa_hip.h (its declarations sit inside a visibility
 # pragma) and nothing else -- the helpers the entry-point files share cannot be interposed by another library of the process
@@ -36,10 +36,14 @@ FLAGS = ['-O3', '-std=c++17', '-fPIC', '--offload-arch=' + ARCH, '-fno-gpu-rdc',
 # `#pragma clang fp contract(off)` does not do it: the back end keeps fusing under the command line's `fast`.)
 # The unit-cell kernels compute their coordinates as the reference does, a * b + c * d without fused operations, so that a
 # pixel lands in the bin NumPy puts it in.
+# The Kerelsky kernel runs the very header the host check compiles (tests/host/kerelsky_check.cpp, also unfused): with contraction
+# off both perform one sequence of rounded operations and differ only in their maths libraries' sincos and atan2, and
+# A = A0 + A0 J comes out with the roundings of the element-wise NumPy expression, which the a0 = NULL entry is held equal to.
+# The solver's products are few beside its sincos, divisions and square roots, so fusing them would buy little.
 # (gpa_wff.hip needs no entry: its instantiations for 1, 2, 4 and 8 thresholds must round alike, and they do because every
 # product-sum there is an explicit fma() -- contraction has nothing left to decide.)
 EXTRA_FLAGS = {'gpa_unwrap_rowhalf.hip': ['-ffp-contract=off'], 'gpa_unwrap_rowhalfpers.hip': ['-ffp-contract=off'],
-               'gpa_ucell.hip': ['-ffp-contract=off']}
+               'gpa_ucell.hip': ['-ffp-contract=off'], 'gpa_kerelsky.hip': ['-ffp-contract=off']}
 
 
 def flags_for(tu):

@@ -259,6 +259,13 @@ hipError_t launch_cabs(int dtype, const void* z, size_t count, void* out, hipStr
 hipError_t launch_props(int dtype, const void* jac, size_t npx, int add_identity, double refangle, double refscale,
                         int diff, void* out, hipStream_t s);
 
+// Kerelsky fits (gpa_kerelsky.hip): jac npx x 2 x 2 (J with a0, else A itself) -> out npx x 4 in the dtype, cost (nullable) in f64
+struct KerelskyArgs {
+  double a0[4], x0[4], retry_cost;
+  int max_nfev, has_a0;
+};
+hipError_t launch_kerelsky(int dtype, const void* jac, size_t npx, const KerelskyArgs& p, void* out, double* cost, hipStream_t s);
+
 // f-4: one IRLS pass of the Huber plane fit; ten sums at scratch + huber_sums_offset() (scratch: 10 more doubles than that)
 int huber_sums_offset();
 hipError_t launch_huber_moments(int dtype, const void* img, int n0, int n1, const double* coef, double cx, double cy,

@@ -7,8 +7,15 @@ weighted least squares of the phase gradients and the 2x2 singular value decompo
 runs in libgpa_hip.so (gpa_phasegradient2J / gpa_props_from_jac, include/gpa_hip.h); the
 k-vector bookkeeping on P x 2 arrays stays on the host.  No CPU fallback.
 
-The Kerelsky fits, the double-strain decomposition and the dask per-pixel least squares of
-the reference module are out of scope.
+The Kerelsky decomposition of the displacement-gradient field -- Kerelsky_Jac, Kerelsky_J and its per-pixel worker
+iterate_J_leastsq (property_extract.py:696-883) -- runs in the same library (gpa_kerelsky_fit, one bounded Levenberg-Marquardt
+solve per pixel and lane, csrc/gpa_kerelsky.h) in place of scipy.optimize.least_squares behind a dask gufunc; Kerelsky_J_dev is its
+device-resident form.  The four `latticegen` functions behind the model are restated.  Differences, all stated at
+the functions: `lq_kwargs` takes `max_nfev` only; a pixel with a non-finite Jacobian gives NaN where the reference raises; a global
+fit counts as failed when its result is not finite.
+
+Kerelsky, Kerelsky_plus and moire_amplitudes (fits of the k-vector lengths, no per-pixel work) and double_strain_decomp (marked
+UNTESTED in the reference, prints from its loop) are out of scope.
 """
 import numpy as np
 
@@ -81,3 +88,133 @@ def calc_props_from_phasegradient(kvecs, grads, weights, nmperpixel, dtype=None)
     J = phasegradient2J(kvecs, grads, weights, nmperpixel, dtype=dtype)
     _, theta_0, _ = get_initial_props(kvecs)
     return props_from_J(J, refangle=theta_0, dtype=dtype)
+
+
+# ---- Kerelsky decomposition (property_extract.py:457-479, :696-883) ----------------------------------------------------------
+KERELSKY_DELTA = 0.16          # Poisson ratio of the strain matrix, as calc_abcd's delta (property_extract.py:511)
+
+
+def _rot(angle_deg):
+    a = np.deg2rad(angle_deg)
+    return np.array([[np.cos(a), -np.sin(a)], [np.sin(a), np.cos(a)]])
+
+
+def twist_matrix(angle):
+    """W(angle / 2) - W(-angle / 2), the transformation of a lattice twist over `angle` degrees (property_extract.py:457-479)."""
+    return 2 * np.sin(np.deg2rad(angle / 2)) * np.array([[0., -1.], [1., 0.]])
+
+
+def Jac_fit_diff(x, JacA0):
+    """The residual the Kerelsky fits minimise (property_extract.py:696-704), on the host: for x = (theta, psi, epsilon, xi),
+    angles in degrees, 1000 ravel(V^T D V W(theta + xi) - W(xi) - JacA0) with W the rotation, V = W(psi) and
+    D = diag(1 / (1 + epsilon), 1 / (1 - 0.16 epsilon))."""
+    theta, psi, epsilon, xi = x
+    V = _rot(psi)
+    D = np.diag([1 / (1 + epsilon), 1 / (1 - KERELSKY_DELTA * epsilon)])
+    return np.ravel(V.T @ D @ V @ _rot(theta + xi) - _rot(xi) - JacA0) * 1000
+
+
+def _fit_dtype(dtype):
+    dtype = np.dtype(_dt(dtype))
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError('dtype must be float32 or float64')
+    return dtype
+
+
+def _max_nfev(lq_kwargs):
+    if lq_kwargs is None:
+        return 50
+    for key in lq_kwargs:
+        if key != 'max_nfev':
+            raise NotImplementedError('lq_kwargs[%r]: the device solver takes max_nfev only (its tolerances are fixed at the '
+                                      'precision of f64)' % (key,))
+    n = lq_kwargs.get('max_nfev', 50)
+    if n is None:
+        return 400                                   # scipy's default, 100 * the number of parameters
+    if int(n) != n or n < 1:
+        raise ValueError('lq_kwargs["max_nfev"] must be an integer >= 1')
+    return int(n)
+
+
+def _kerelsky_a0(kvecs, nmperpixel, a_0, reference, sort):
+    """A0 with k0s @ A0.T = kvecs / r_k0 for the unit vectors k0s at 0, 60, 120 degrees, and the start of the global fit
+    (property_extract.py:748-762): every argument checked."""
+    kvecs = np.asarray(kvecs, dtype=np.float64)
+    if kvecs.shape != (3, 2):
+        raise ValueError('kvecs must have shape (3, 2)')
+    if not np.isfinite(kvecs).all():
+        raise ValueError('kvecs must be finite')
+    if not (np.isfinite(nmperpixel) and nmperpixel > 0 and np.isfinite(a_0) and a_0 > 0):
+        raise ValueError('nmperpixel and a_0 must be positive')
+    if reference not in (None, 'symmetric'):
+        raise ValueError("reference must be None or 'symmetric'")
+    if sort not in (-1, 0, 1):
+        raise ValueError('sort must be -1, 0 or 1')
+    angles = np.arctan2(kvecs[:, 1], kvecs[:, 0])
+    r_k0 = nmperpixel / (a_0 * np.sin(np.deg2rad(60.)))
+    lkvecs = kvecs / r_k0
+    if sort != 0:
+        lkvecs = lkvecs[np.argsort(sort * periodic_difference(angles, periodic_average(angles)))]
+    k0 = np.deg2rad([0., 60., 120.])
+    A0 = np.linalg.lstsq(np.stack([np.cos(k0), np.sin(k0)], axis=1), lkvecs, rcond=None)[0].T
+    est = np.array([.01, 0., 0., np.rad2deg(np.arctan2(lkvecs[0, 1], lkvecs[0, 0])) % 360])
+    return np.ascontiguousarray(A0), est
+
+
+def _global_fit(A0, est, max_nfev, debug):
+    """the fit of A0 itself, one pixel: starts est and est with psi = 90, the second whenever the first leaves a cost above 1e-20
+    (property_extract.py:763-768)"""
+    x, cost = _lib.kerelsky_fit(A0, est, max_nfev=max_nfev, retry_cost=1e-20, dtype=np.float64)
+    if debug:
+        print('Kerelsky global fit: x = %s, cost = %s' % (x, cost))
+    return x if np.isfinite(x).all() else np.full(4, np.nan)
+
+
+def iterate_J_leastsq(JacA0, refest, lq_kwargs=None, dtype=None):
+    """The fit of every 2 x 2 matrix of JacA0 (..., 2, 2) from the start refest (property_extract.py:863-883): array (..., 4) of
+    (theta, psi, epsilon, xi).  A second start at psi + 90 is tried where the first leaves a cost above 1e-5."""
+    return _lib.kerelsky_fit(JacA0, refest, max_nfev=_max_nfev(lq_kwargs), retry_cost=1e-5, dtype=_fit_dtype(dtype))[0]
+
+
+def Kerelsky_Jac(kvecs, nmperpixel=1., a_0=0.246, reference=None, debug=False, sort=0):
+    """(theta, psi, epsilon, xi) of three k-vectors (unit cells per pixel), in degrees (property_extract.py:707-777), by the fit of
+    JacA0 with k0s @ JacA0.T = kvecs.  reference='symmetric' adds theta / 2 to xi.  NaN when the fit fails, i.e. when its result
+    is not finite."""
+    A0, est = _kerelsky_a0(kvecs, nmperpixel, a_0, reference, sort)
+    params = _global_fit(A0, est, 400, debug)
+    if reference == 'symmetric':
+        params[3] = params[3] + params[0] / 2
+    return params
+
+
+def Kerelsky_J(J, kvecs, nmperpixel=1., a_0=0.246, reference=None, debug=False, sort=0, lq_kwargs={'max_nfev': 50}, dtype=None):
+    """Per-pixel (theta, psi, epsilon, xi) from the displacement-gradient field J (..., 2, 2) and the three k-vectors
+    (property_extract.py:780-860): returns (X (..., 4), refest), X from the fit of A0 + A0 J at every pixel started at the global
+    fit refest of A0; or the NaN refest alone when the global fit fails.  As in the reference, `reference` has no effect here.
+    A pixel whose J is not finite gives NaN (the reference raises)."""
+    max_nfev, dtype = _max_nfev(lq_kwargs), _fit_dtype(dtype)
+    J = np.asarray(J)
+    if J.ndim < 2 or J.shape[-2:] != (2, 2):
+        raise ValueError('J must have shape (..., 2, 2)')
+    A0, est = _kerelsky_a0(kvecs, nmperpixel, a_0, reference, sort)
+    refest = _global_fit(A0, est, max_nfev, debug)
+    if not np.isfinite(refest).all():
+        return refest
+    X, _ = _lib.kerelsky_fit(J, refest, a0=A0, max_nfev=max_nfev, retry_cost=1e-5, dtype=dtype)
+    return X, refest
+
+
+def Kerelsky_J_dev(J_ptr, npx, kvecs, nmperpixel=1., a_0=0.246, reference=None, debug=False, sort=0, lq_kwargs={'max_nfev': 50},
+                   dtype=None, out_ptr=None, cost_ptr=None, device=0, stream=None):
+    """Kerelsky_J for a J that is resident on the device (e.g. the output of Plan.phasegradient2J_dev): J_ptr holds npx x 2 x 2
+    values of `dtype`, out_ptr receives npx x 4 of them (cost_ptr, optional, npx doubles); asynchronous on `stream`.  Returns
+    refest; when the global fit fails refest is NaN and nothing is written."""
+    max_nfev, dtype = _max_nfev(lq_kwargs), _fit_dtype(dtype)
+    if out_ptr is None:
+        raise ValueError('out_ptr is required')
+    A0, est = _kerelsky_a0(kvecs, nmperpixel, a_0, reference, sort)
+    refest = _global_fit(A0, est, max_nfev, debug)
+    if np.isfinite(refest).all():
+        _lib.kerelsky_fit_dev(J_ptr, npx, refest, out_ptr, a0=A0, max_nfev=max_nfev, retry_cost=1e-5, cost_ptr=cost_ptr,
+                              dtype=dtype, device=device, stream=stream)
+    return refest
