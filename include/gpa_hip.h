@@ -406,6 +406,41 @@ int gpa_kerelsky_fit_dev(int device, int dtype, size_t npx, const void* jac, con
                          const double* x0, int max_nfev, double retry_cost, void* out, double* cost,
                          void* stream);
 
+/* Jacobian J = grad(-u) and lattice-property maps straight from a displacement field or from phases, one pass over the data;
+ * replaces u2J / u2Jac (property_extract.py:13-26), phases2J / phases2Jac (:29-52), calc_props_from_phases (:258-278) and
+ * phys_props_from_Jac (:181-217).  None needs a plan.
+ * gpa_field_jacobian: u is nimg x 2 x n0 x n1; J[f, n, m, c, a] = np.gradient(-u[f, c], nmperpixel, axis=a), nimg x n0 x n1 x 2 x 2:
+ *   central differences over 2 nmperpixel inside, one-sided ones over nmperpixel at the first and last sample of an axis, each
+ *   one subtraction and one division by the divisor rounded to the dtype.  Frames are independent.
+ * gpa_phases_jacobian: phases and weights are P x n0 x n1, 2 <= P <= 8, kvecs P x 2 (host).  Per peak and axis
+ *   b = wrapToPi(2 np.gradient(phase)) / 2 / nmperpixel; J = -(per-pixel weighted least squares of b against 2 pi kvecs), the solve
+ *   of gpa_phasegradient2J; 0 where every weight is 0.
+ * Both: J and props may each be NULL, not both.  With add_identity the stored J is I + J (the ...Jac spellings).  props is
+ *   nimg x 4 x n0 x n1 = gpa_props_from_jac(add_identity = 1) of the plain J, bit for bit, with the same refangle, refscale, diff.
+ *   A device J must be aligned to 4 elements.  An output must not overlap an input or the other output.
+ * gpa_phys_props_from_jac: jac npx x 2 x 2 -> props 4 x npx = (angle + refangle, aniangle, alpha refscale, epsilon) with
+ *   epsilon = (s0 - s1) / (s0 + poisson_ratio s1) of the singular values s0 >= s1, alpha = s1 (1 + epsilon), or
+ *   s0 / (1 + epsilon) with diff (which also turns aniangle by 90 degrees before the mod 180).
+ * Argument errors (GPA_ERR_ARG) name the argument and come before any device is touched: an axis < 2, nimg < 1, P outside
+ * 2 ... 8, nmperpixel zero or not finite, both outputs NULL, overlapping buffers.  _dev: device pointers (kvecs stays a host
+ * pointer), asynchronous on the given hipStream_t, no allocation and no synchronisation.                                    */
+int gpa_field_jacobian(int device, int dtype, int nimg, int n0, int n1, const void* u, double nmperpixel,
+                       int add_identity, void* J, void* props, double refangle, double refscale, int diff);
+int gpa_field_jacobian_dev(int device, int dtype, int nimg, int n0, int n1, const void* u, double nmperpixel,
+                           int add_identity, void* J, void* props, double refangle, double refscale, int diff,
+                           void* stream);
+int gpa_phases_jacobian(int device, int dtype, int n0, int n1, int P, const double* kvecs, const void* phases,
+                        const void* weights, double nmperpixel, int add_identity, void* J, void* props,
+                        double refangle, double refscale, int diff);
+int gpa_phases_jacobian_dev(int device, int dtype, int n0, int n1, int P, const double* kvecs, const void* phases,
+                            const void* weights, double nmperpixel, int add_identity, void* J, void* props,
+                            double refangle, double refscale, int diff, void* stream);
+int gpa_phys_props_from_jac(int device, int dtype, size_t npx, const void* jac, int add_identity, double refangle,
+                            double refscale, int diff, double poisson_ratio, void* props);
+int gpa_phys_props_from_jac_dev(int device, int dtype, size_t npx, const void* jac, int add_identity,
+                                double refangle, double refscale, int diff, double poisson_ratio, void* props,
+                                void* stream);
+
 /* f-4 -- robust plane fit a0*x + a1*y + a2 (x = row, y = column index) through an n0 x n1 map:
  * the minimiser of the Huber cost that fit_plane (mathtools.py:30-47, scipy least_squares with
  * loss='huber', f_scale 1, start at 0) approaches, by iteratively reweighted least squares with the

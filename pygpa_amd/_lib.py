@@ -90,6 +90,12 @@ SIGNATURES = {
     'gpa_props_from_jac_dev': (_i, [_i, _i, _sz, _vp, _i, _d, _d, _i, _vp, _vp]),
     'gpa_kerelsky_fit': (_i, [_i, _i, _sz, _vp, _vp, _vp, _i, _d, _vp, _vp]),
     'gpa_kerelsky_fit_dev': (_i, [_i, _i, _sz, _vp, _vp, _vp, _i, _d, _vp, _vp, _vp]),
+    'gpa_field_jacobian': (_i, [_i, _i, _i, _i, _i, _vp, _d, _i, _vp, _vp, _d, _d, _i]),
+    'gpa_field_jacobian_dev': (_i, [_i, _i, _i, _i, _i, _vp, _d, _i, _vp, _vp, _d, _d, _i, _vp]),
+    'gpa_phases_jacobian': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _d, _i, _vp, _vp, _d, _d, _i]),
+    'gpa_phases_jacobian_dev': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _d, _i, _vp, _vp, _d, _d, _i, _vp]),
+    'gpa_phys_props_from_jac': (_i, [_i, _i, _sz, _vp, _i, _d, _d, _i, _d, _vp]),
+    'gpa_phys_props_from_jac_dev': (_i, [_i, _i, _sz, _vp, _i, _d, _d, _i, _d, _vp, _vp]),
     'gpa_fit_plane': (_i, [_vp, _vp, _i, _d, _dp, _ip]),
     'gpa_fit_plane_dev': (_i, [_vp, _vp, _i, _d, _dp, _ip]),
     'gpa_fit_planes_dev': (_i, [_vp, _vp, _i, _i, _d, _vp, _vp]),
@@ -1455,6 +1461,137 @@ def kerelsky_fit_dev(jac_ptr, npx, x0, out_ptr, a0=None, max_nfev=50, retry_cost
     check(load().gpa_kerelsky_fit_dev(int(device), code, int(npx), _ptr(int(jac_ptr)), None if a0 is None else _ptr(a0), _ptr(x0),
                                       max_nfev, retry_cost, _ptr(int(out_ptr)), None if cost_ptr is None else _ptr(int(cost_ptr)),
                                       None if stream is None else _ptr(int(stream))), 'gpa_kerelsky_fit_dev')
+
+
+def _real_dtype(dtype):
+    dtype = np.dtype(dtype)
+    if dtype not in (np.dtype(np.float32), np.dtype(np.float64)):
+        raise ValueError('dtype must be float32 or float64')
+    return dtype, GPA_F32 if dtype == np.float32 else GPA_F64
+
+
+def _spacing(nmperpixel):
+    h = float(nmperpixel)
+    if not np.isfinite(h) or h == 0.0:
+        raise ValueError('nmperpixel must be finite and not zero')
+    return h
+
+
+def _stream(stream):
+    return None if stream is None else _ptr(int(stream))
+
+
+def field_jacobian_shape(shape):
+    """(nimg, n0, n1) of a displacement field (2, N, M) or stack (B, 2, N, M); ValueError for anything else"""
+    shape = tuple(int(v) for v in shape)
+    if len(shape) == 3:
+        shape = (1,) + shape
+    if len(shape) != 4 or shape[1] != 2 or shape[0] < 1:
+        raise ValueError('U must be a displacement field (2, N, M) or a stack (B, 2, N, M), not %s' % (shape,))
+    if shape[2] < 2 or shape[3] < 2:
+        raise ValueError('every axis of U needs at least two samples for a difference, not %s' % (shape[2:],))
+    return shape[0], shape[2], shape[3]
+
+
+def field_jacobian(u, nmperpixel, add_identity=False, want_J=True, want_props=False, refangle=0., refscale=1., diff=False,
+                   dtype=np.float64, device=0):
+    """Plan-free gpa_field_jacobian: u (2, N, M) or (B, 2, N, M) -> (J (..., N, M, 2, 2) or None, props (..., 4, N, M) or None),
+    J = np.gradient(-u, nmperpixel) per component and axis (+ I with add_identity), props those of I + J."""
+    dtype, code = _real_dtype(dtype)
+    h = _spacing(nmperpixel)
+    nimg, n0, n1 = field_jacobian_shape(np.shape(u))
+    if not (want_J or want_props):
+        raise ValueError('nothing to compute: neither J nor props is wanted')
+    lead = np.shape(u)[:-3]
+    u = np.ascontiguousarray(u, dtype=dtype)
+    J = np.empty(lead + (n0, n1, 2, 2), dtype=dtype) if want_J else None
+    props = np.empty(lead + (4, n0, n1), dtype=dtype) if want_props else None
+    check(load().gpa_field_jacobian(int(device), code, nimg, n0, n1, _ptr(u), h, int(bool(add_identity)), _ptr(J), _ptr(props),
+                                    float(refangle), float(refscale), int(bool(diff))), 'gpa_field_jacobian')
+    return J, props
+
+
+def field_jacobian_dev(u_ptr, shape, nmperpixel, J_ptr=None, props_ptr=None, add_identity=False, refangle=0., refscale=1.,
+                       diff=False, dtype=np.float64, device=0, stream=None):
+    """gpa_field_jacobian_dev on device pointers: u of `shape` (2, N, M) or (B, 2, N, M), J and props as field_jacobian lays them
+    out, at least one of them; asynchronous on `stream` (a hipStream_t as an integer; None: the default stream)."""
+    dtype, code = _real_dtype(dtype)
+    h = _spacing(nmperpixel)
+    nimg, n0, n1 = field_jacobian_shape(shape)
+    if J_ptr is None and props_ptr is None:
+        raise ValueError('nothing to compute: J_ptr and props_ptr are both None')
+    check(load().gpa_field_jacobian_dev(int(device), code, nimg, n0, n1, _ptr(int(u_ptr)), h, int(bool(add_identity)),
+                                        None if J_ptr is None else _ptr(int(J_ptr)),
+                                        None if props_ptr is None else _ptr(int(props_ptr)), float(refangle), float(refscale),
+                                        int(bool(diff)), _stream(stream)), 'gpa_field_jacobian_dev')
+
+
+def _phases_args(kvecs, phases_shape, weights_shape):
+    kvecs = _f64(kvecs)
+    if kvecs.ndim != 2 or kvecs.shape[1] != 2 or not 2 <= len(kvecs) <= 8:
+        raise ValueError('kvecs must have shape (P, 2) with 2 <= P <= 8, not %s' % (kvecs.shape,))
+    if not np.isfinite(kvecs).all():
+        raise ValueError('kvecs must be finite')
+    phases_shape = tuple(int(v) for v in phases_shape)
+    if len(phases_shape) != 3 or phases_shape[0] != len(kvecs):
+        raise ValueError('phases must have shape (P, N, M) with one plane per k-vector, not %s' % (phases_shape,))
+    if tuple(weights_shape) != phases_shape:
+        raise ValueError('weights %s must have the shape of phases %s' % (tuple(weights_shape), phases_shape))
+    if phases_shape[1] < 2 or phases_shape[2] < 2:
+        raise ValueError('every axis of phases needs at least two samples for a difference, not %s' % (phases_shape[1:],))
+    return kvecs
+
+
+def phases_jacobian(kvecs, phases, weights, nmperpixel, add_identity=False, want_J=True, want_props=False, refangle=0., refscale=1.,
+                    diff=False, dtype=np.float64, device=0):
+    """Plan-free gpa_phases_jacobian: phases and weights (P, N, M), kvecs (P, 2) -> (J (N, M, 2, 2) or None, props (4, N, M) or
+    None)."""
+    dtype, code = _real_dtype(dtype)
+    h = _spacing(nmperpixel)
+    kvecs = _phases_args(kvecs, np.shape(phases), np.shape(weights))
+    if not (want_J or want_props):
+        raise ValueError('nothing to compute: neither J nor props is wanted')
+    phases = np.ascontiguousarray(phases, dtype=dtype)
+    weights = np.ascontiguousarray(weights, dtype=dtype)
+    P, n0, n1 = phases.shape
+    J = np.empty((n0, n1, 2, 2), dtype=dtype) if want_J else None
+    props = np.empty((4, n0, n1), dtype=dtype) if want_props else None
+    check(load().gpa_phases_jacobian(int(device), code, n0, n1, P, _ptr(kvecs), _ptr(phases), _ptr(weights), h,
+                                     int(bool(add_identity)), _ptr(J), _ptr(props), float(refangle), float(refscale),
+                                     int(bool(diff))), 'gpa_phases_jacobian')
+    return J, props
+
+
+def phases_jacobian_dev(kvecs, phases_ptr, weights_ptr, shape, nmperpixel, J_ptr=None, props_ptr=None, add_identity=False,
+                        refangle=0., refscale=1., diff=False, dtype=np.float64, device=0, stream=None):
+    """gpa_phases_jacobian_dev on device pointers: phases and weights of `shape` (P, N, M); J and props as phases_jacobian lays
+    them out, at least one of them; asynchronous on `stream`."""
+    dtype, code = _real_dtype(dtype)
+    h = _spacing(nmperpixel)
+    kvecs = _phases_args(kvecs, shape, shape)
+    if J_ptr is None and props_ptr is None:
+        raise ValueError('nothing to compute: J_ptr and props_ptr are both None')
+    P, n0, n1 = (int(v) for v in shape)
+    check(load().gpa_phases_jacobian_dev(int(device), code, n0, n1, P, _ptr(kvecs), _ptr(int(phases_ptr)), _ptr(int(weights_ptr)),
+                                         h, int(bool(add_identity)), None if J_ptr is None else _ptr(int(J_ptr)),
+                                         None if props_ptr is None else _ptr(int(props_ptr)), float(refangle), float(refscale),
+                                         int(bool(diff)), _stream(stream)), 'gpa_phases_jacobian_dev')
+
+
+def phys_props_from_jac(jac, add_identity=False, refangle=0., refscale=1., diff=False, poisson_ratio=0.16, dtype=np.float64,
+                        device=0):
+    """Plan-free gpa_phys_props_from_jac: jac (..., 2, 2) -> (angle, aniangle, alpha, epsilon) as (4, ...)."""
+    dtype, code = _real_dtype(dtype)
+    if not np.isfinite(poisson_ratio):
+        raise ValueError('poisson_ratio must be finite')
+    if np.shape(jac)[-2:] != (2, 2):
+        raise ValueError('jac must have shape (..., 2, 2)')
+    jac = np.ascontiguousarray(jac, dtype=dtype)
+    props = np.empty((4,) + jac.shape[:-2], dtype=dtype)
+    check(load().gpa_phys_props_from_jac(int(device), code, jac.size // 4, _ptr(jac), int(bool(add_identity)), float(refangle),
+                                         float(refscale), int(bool(diff)), float(poisson_ratio), _ptr(props)),
+          'gpa_phys_props_from_jac')
+    return props
 
 
 @atexit.register

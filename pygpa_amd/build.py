@@ -20,7 +20,8 @@ LIB = os.path.join(HERE, 'libgpa_hip.so')
 SOURCES = ['gpa_sweep.hip', 'gpa_passb_shared.hip', 'gpa_sweep_ext.hip', 'gpa_reconstruct.hip', 'gpa_unwrap.hip', 'gpa_unwrap_rows.hip', 'gpa_unwrap_rowhalf.hip', 'gpa_unwrap_pqdct.hip', 'gpa_unwrap_rowpers.hip', 'gpa_unwrap_rowhalfpers.hip', 'gpa_unwrap_cols.hip', 'gpa_unwrap_colhalf.hip', 'gpa_unwrap_colstream.hip', 'gpa_unwrap_stencil.hip', 'gpa_unwrap_generic.hip',
            'gpa_unwrap_tables.hip', 'gpa_dft2.hip', 'gpa_gaussfft.hip', 'gpa_warp.hip', 'gpa_tiles.hip', 'gpa_peaks.hip', 'gpa_api.hip', 'gpa_api_tables.hip', 'gpa_api_sweep.hip', 'gpa_api_unwrap.hip', 'gpa_api_driver.hip',
            'gpa_api_tiles.hip', 'gpa_api_warp.hip', 'gpa_api_spectral.hip', 'gpa_ucell.hip', 'gpa_api_ucell.hip', 'gpa_iterate.hip', 'gpa_api_iterate.hip', 'gpa_wff.hip', 'gpa_api_wff.hip',
-           'gpa_prep.hip', 'gpa_api_prep.hip', 'gpa_lines.hip', 'gpa_api_lines.hip', 'gpa_kerelsky.hip', 'gpa_api_kerelsky.hip']
+           'gpa_prep.hip', 'gpa_api_prep.hip', 'gpa_lines.hip', 'gpa_api_lines.hip', 'gpa_kerelsky.hip', 'gpa_api_kerelsky.hip',
+           'gpa_fieldjac.hip', 'gpa_api_fieldjac.hip']
 ARCH = 'gfx950'
 # -fvisibility=hidden: the dynamic symbol table is the C ABI of include/gpa_hip.h (its declarations sit inside a visibility
 # pragma) and nothing else -- the helpers the entry-point files share cannot be interposed by another library of the process

@@ -266,6 +266,17 @@ struct KerelskyArgs {
 };
 hipError_t launch_kerelsky(int dtype, const void* jac, size_t npx, const KerelskyArgs& p, void* out, double* cost, hipStream_t s);
 
+// Field or phases -> J and properties in one pass (gpa_fieldjac.hip, geometry in gpa_fieldjac.h): u nimg x 2 x n0 x n1, or phases
+// and weights P x n0 x n1 with kvecs a host P x 2 array; J (nimg x n0 x n1 x 2 x 2, + I with add_identity) and props
+// (nimg x 4 x n0 x n1, of I + J) are nullable, not both.  Physical decomposition of a Jacobian: npx x 2 x 2 -> 4 x npx.
+hipError_t launch_field_jacobian(int dtype, int nimg, int n0, int n1, const void* u, double nmperpixel, int add_identity, void* J,
+                                 void* props, double refangle, double refscale, int diff, hipStream_t s);
+hipError_t launch_phases_jacobian(int dtype, int n0, int n1, int P, const double* kvecs, const void* phases, const void* weights,
+                                  double nmperpixel, int add_identity, void* J, void* props, double refangle, double refscale,
+                                  int diff, hipStream_t s);
+hipError_t launch_phys_props(int dtype, const void* jac, size_t npx, int add_identity, double refangle, double refscale, int diff,
+                             double poisson_ratio, void* out, hipStream_t s);
+
 // f-4: one IRLS pass of the Huber plane fit; ten sums at scratch + huber_sums_offset() (scratch: 10 more doubles than that)
 int huber_sums_offset();
 hipError_t launch_huber_moments(int dtype, const void* img, int n0, int n1, const double* coef, double cx, double cy,

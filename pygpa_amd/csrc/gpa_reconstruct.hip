@@ -7,32 +7,9 @@
 // rank-deficient pixels, 0 where every weight is 0).  MFMA has nothing to offer
 // a 3x2 problem per pixel; the kernel is HBM-bound.
 #include "gpa_internal.h"
+#include "gpa_jacmath.h"   // Consts, wrap_to_pi, wrap_phase_diff, wrap_to_pi_fast, solve2, Quad, lattice_props
 
 namespace gpa {
-
-template <class T> struct Consts;
-template <> struct Consts<float> {
-  static constexpr float pi = 3.14159265358979323846f, two_pi = 6.28318530717958647692f;
-};
-template <> struct Consts<double> {
-  static constexpr double pi = 3.14159265358979323846, two_pi = 6.28318530717958647692;
-};
-
-// (x + pi) mod 2 pi - pi with floored mod: [-pi, pi), +pi -> -pi (mathtools.py:72-75)
-template <class T>
-__device__ __forceinline__ T wrap_to_pi(T x) {
-  const T t = x + Consts<T>::pi;
-  return t - Consts<T>::two_pi * floor(t / Consts<T>::two_pi) - Consts<T>::pi;
-}
-
-// the same for the difference of two phases, |x| < 2 pi: floor((x + pi) / 2 pi) is -1, 0 or 1 and follows from
-// two comparisons -- no division, and (like NumPy's exact float modulo) no quotient rounding at the seams
-template <class T>
-__device__ __forceinline__ T wrap_phase_diff(T x) {
-  const T t = x + Consts<T>::pi;
-  const T r = t >= Consts<T>::two_pi ? t - Consts<T>::two_pi : (t < T(0) ? t + Consts<T>::two_pi : t);
-  return r - Consts<T>::pi;
-}
 
 // wrap(d + step) for a phase difference d of two atan2 results and a CONSTANT step = hi + lo (raw winners, see
 // reconstruct_setup_kernel), without the systematic rounding that wrap_phase_diff(d + hi) has: d is a multiple of the
@@ -53,29 +30,6 @@ __device__ __forceinline__ T wrap_diff_plus_step(T d, T hi, T lo) {
 // Consts<T>::two_pi) over the true 2 pi: 1 + 2.78e-8 in f32, 1 in f64
 template <class T> __device__ __forceinline__ double unwrap_turn_scale() {
   return (double)Consts<T>::two_pi / 6.28318530717958647692;
-}
-
-// general argument, fast path for the usual |x| < 2 pi (same arithmetic as wrap_to_pi there)
-template <class T>
-__device__ __forceinline__ T wrap_to_pi_fast(T x) {
-  return fabs(x) < Consts<T>::two_pi ? wrap_phase_diff(x) : wrap_to_pi(x);
-}
-
-template <class T>
-__device__ __forceinline__ void solve2(T a00, T a01, T a11, T r0, T r1, T& x0, T& x1) {
-  const T det = a00 * a11 - a01 * a01, tr = a00 + a11;
-  const T tiny = sizeof(T) == 4 ? T(1e-12) : T(1e-28);
-  if (det > tiny * tr * tr) {
-    const T inv = T(1) / det;
-    x0 = (a11 * r0 - a01 * r1) * inv;
-    x1 = (a00 * r1 - a01 * r0) * inv;
-  } else if (tr > T(0)) {
-    x0 = r0 / tr;
-    x1 = r1 / tr;
-  } else {
-    x0 = T(0);
-    x1 = T(0);
-  }
 }
 
 constexpr int MAXP = 8;
@@ -503,7 +457,6 @@ hipError_t launch_wlstsq(int dtype, const void* b, const void* w, const double* 
 // iso_ref=False (property_extract.py:69-101).  One thread per pixel, both solves share the normal
 // matrix; grads are read as (d/dx, d/dy) pairs, J leaves as one 4-element store.
 template <class T> struct alignas(2 * sizeof(T)) Pair2 { T x, y; };
-template <class T> struct alignas(4 * sizeof(T)) Quad { T a, b, c, d; };
 
 // shift.on: gradients are taken relative to the isotropic lattice kvecs + dks, g <- wrapToPi(g - 2 pi dk)
 // (iso_ref=True, :87-92); kmat then already holds 2 pi (kvecs + dks).
@@ -537,34 +490,18 @@ __global__ __launch_bounds__(256) void jacobian_kernel(const Pair2<T>* __restric
 }
 
 // (angle, aniangle, alpha, kappa) per pixel from the 2x2 Jacobian of the lattice transformation:
-// props_from_Jac (property_extract.py:137-178).  The reference takes a LAPACK SVD and normalises
-// the signs of U; for a 2x2 matrix the same quantities come in closed form from
-//   E,H = (a+d)/2, (c-b)/2   (rotation part),   F,G = (a-d)/2, (c+b)/2   (shear part):
-//   s0,s1 = Q+R, |Q-R| with Q=|(E,H)|, R=|(F,G)|; U = rot((atan2(H,E)+atan2(G,F))/2);
-//   U V^T = rot(atan2(H,E)) for det>0 and the reflection of angle -atan2(G,F) for det<0.
+// props_from_Jac (property_extract.py:137-178), the closed form of gpa_jacmath.h.
 template <class T>
 __global__ __launch_bounds__(256) void props_kernel(const Quad<T>* __restrict__ jac, size_t npx, T ident,
                                                    T refangle, T refscale, int diff, T* __restrict__ out) {
   const size_t o = (size_t)blockIdx.x * 256 + threadIdx.x;
   if (o >= npx) return;
-  const Quad<T> j = jac[o];
-  T a = j.a + ident, b = j.b, c = j.c, d = j.d + ident;
-  // scale by the largest entry: the squares below must not leave the range of T
-  const T m = fmax(fmax(fabs(a), fabs(b)), fmax(fabs(c), fabs(d)));
-  const T im = m > T(0) ? T(1) / m : T(0);
-  a *= im; b *= im; c *= im; d *= im;
-  const T E = T(0.5) * (a + d), F = T(0.5) * (a - d), G = T(0.5) * (c + b), H = T(0.5) * (c - b);
-  const T Q = sqrt(E * E + H * H), R = sqrt(F * F + G * G);
-  const T s0 = Q + R, s1 = fabs(Q - R);
-  const T a1 = atan2(G, F), a2 = atan2(H, E);
-  const T deg = T(180) / Consts<T>::pi;
-  const T angle = (Q >= R ? a2 : -a1) * deg;
-  T ani = T(-0.5) * (a1 + a2) * deg + (diff ? T(90) : T(0));
-  ani -= T(180) * floor(ani / T(180));
-  out[o] = angle + refangle;
-  out[npx + o] = ani;
-  out[2 * npx + o] = (diff ? s0 : s1) * m * refscale;
-  out[3 * npx + o] = s0 / s1;
+  T p[4];
+  lattice_props(jac[o], ident, refangle, refscale, diff, p);
+  out[o] = p[0];
+  out[npx + o] = p[1];
+  out[2 * npx + o] = p[2];
+  out[3 * npx + o] = p[3];
 }
 
 // |z| of a complex array (np.abs of the lock-ins: the weights of phasegradient2J), two values per thread

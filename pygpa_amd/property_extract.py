@@ -7,6 +7,13 @@ weighted least squares of the phase gradients and the 2x2 singular value decompo
 runs in libgpa_hip.so (gpa_phasegradient2J / gpa_props_from_jac, include/gpa_hip.h); the
 k-vector bookkeeping on P x 2 arrays stays on the host.  No CPU fallback.
 
+J straight from a displacement field or from phases -- u2J, u2Jac, phases2J, phases2Jac, calc_props_from_phases, phys_props_from_Jac
+(property_extract.py:13-52, :181-217, :258-278) and the stack form u2J_stack -- is one pass over the data (gpa_field_jacobian,
+gpa_phases_jacobian, gpa_phys_props_from_jac): the difference stencil, the per-pixel solve and the 2 x 2 SVD in one
+kernel, with J, the properties of 1 + J, or both as outputs; u2J_dev and phases2J_dev are the device-resident forms.  Differences:
+u2Jac works (the reference's loses its spacing argument and raises TypeError); `weights` must have the shape of `phases`; shape
+errors are ValueError before the library is touched.  The moire conversions (J_2_J_diff, moire_props_*, f2angle) are not provided.
+
 The Kerelsky decomposition of the displacement-gradient field -- Kerelsky_Jac, Kerelsky_J and its per-pixel worker
 iterate_J_leastsq (property_extract.py:696-883) -- runs in the same library (gpa_kerelsky_fit, one bounded Levenberg-Marquardt
 solve per pixel and lane, csrc/gpa_kerelsky.h) in place of scipy.optimize.least_squares behind a dask gufunc; Kerelsky_J_dev is its
@@ -90,7 +97,77 @@ def calc_props_from_phasegradient(kvecs, grads, weights, nmperpixel, dtype=None)
     return props_from_J(J, refangle=theta_0, dtype=dtype)
 
 
-# ---- Kerelsky decomposition (property_extract.py:457-479, :696-883) ----------------------------------------------------------
+# ---- J and properties from a displacement field or from phases (property_extract.py:13-52, :181-217, :258-278) ---------------
+def u2J(U, nmperpixel, dtype=None):
+    """J (N, M, 2, 2) from the displacement field U (2, N, M) (property_extract.py:13-18): J[n, m, c, a] is
+    np.gradient(-U[c], nmperpixel, axis=a), to the bit."""
+    if np.ndim(U) != 3:
+        raise ValueError('U must have shape (2, N, M); u2J_stack takes stacks')
+    return _lib.field_jacobian(U, nmperpixel, dtype=_dt(dtype))[0]
+
+
+def u2Jac(U, nmperpixel, dtype=None):
+    """Jac = 1 + u2J(U, nmperpixel) (property_extract.py:21-26, where the call loses nmperpixel and raises TypeError); the identity
+    is added in the kernel."""
+    if np.ndim(U) != 3:
+        raise ValueError('U must have shape (2, N, M)')
+    return _lib.field_jacobian(U, nmperpixel, add_identity=True, dtype=_dt(dtype))[0]
+
+
+def u2J_stack(us, nmperpixel, dtype=None):
+    """u2J of every frame of a stack (B, 2, N, M) in one call: (B, N, M, 2, 2), frame b equal to u2J(us[b]) bit for bit."""
+    if np.ndim(us) != 4:
+        raise ValueError('us must have shape (B, 2, N, M)')
+    return _lib.field_jacobian(us, nmperpixel, dtype=_dt(dtype))[0]
+
+
+def u2J_dev(U_ptr, shape, nmperpixel, J_ptr=None, props_ptr=None, stream=None, add_identity=False, refangle=0., refscale=1.,
+            diff=False, dtype=None, device=0):
+    """u2J for a field that is resident on the device (e.g. the u of extract_displacement_field_stack): U_ptr holds `shape` =
+    (2, N, M) or (B, 2, N, M) values of `dtype`.  J_ptr receives (B,) N x M x 2 x 2 values, props_ptr (B,) 4 x N x M --
+    props_from_J of that J -- in the same pass; at least one of the two.  Asynchronous on `stream`."""
+    _lib.field_jacobian_dev(U_ptr, shape, nmperpixel, J_ptr=J_ptr, props_ptr=props_ptr, add_identity=add_identity,
+                            refangle=refangle, refscale=refscale, diff=diff, dtype=_dt(dtype), device=device, stream=stream)
+
+
+def phases2J(kvecs, phases, weights, nmperpixel, dtype=None):
+    """J (N, M, 2, 2) from phases (P, N, M), e.g. of iterate_GPA or phase_unwrap (property_extract.py:39-52): minus the per-pixel
+    weighted least squares of wrapToPi(2 np.gradient(phases)) / 2 / nmperpixel against 2 pi kvecs.  `weights` must have the shape
+    of `phases`."""
+    return _lib.phases_jacobian(kvecs, phases, weights, nmperpixel, dtype=_dt(dtype))[0]
+
+
+def phases2Jac(kvecs, phases, weights, nmperpixel, dtype=None):
+    """Jac = 1 + phases2J (property_extract.py:29-36); the identity is added in the kernel."""
+    return _lib.phases_jacobian(kvecs, phases, weights, nmperpixel, add_identity=True, dtype=_dt(dtype))[0]
+
+
+def phases2J_dev(kvecs, phases_ptr, weights_ptr, shape, nmperpixel, J_ptr=None, props_ptr=None, stream=None, add_identity=False,
+                 refangle=0., refscale=1., diff=False, dtype=None, device=0):
+    """phases2J for phases and weights resident on the device, `shape` = (P, N, M) values of `dtype` each.  J_ptr receives
+    N x M x 2 x 2 values, props_ptr 4 x N x M -- props_from_J of that J -- in the same pass; at least one of the two.
+    Asynchronous on `stream`."""
+    _lib.phases_jacobian_dev(kvecs, phases_ptr, weights_ptr, shape, nmperpixel, J_ptr=J_ptr, props_ptr=props_ptr,
+                             add_identity=add_identity, refangle=refangle, refscale=refscale, diff=diff, dtype=_dt(dtype),
+                             device=device, stream=stream)
+
+
+def calc_props_from_phases(kvecs, phases, weights, nmperpixel, dtype=None):
+    """Lattice properties directly from phases (property_extract.py:258-278): props_from_Jac(1 + phases2J) with the base angle of
+    kvecs added, in one pass that never stores J."""
+    _, theta_0, _ = get_initial_props(kvecs)
+    return _lib.phases_jacobian(kvecs, phases, weights, nmperpixel, want_J=False, want_props=True, refangle=theta_0,
+                                dtype=_dt(dtype))[1]
+
+
+def phys_props_from_Jac(Jac, refangle=0., refscale=1, diff=False, poisson_ratio=0.16, dtype=None):
+    """(angle, aniangle, alpha, epsilon) of a lattice from the Jacobian of its transformation, the heterostrain epsilon in place of
+    the anisotropy kappa (property_extract.py:181-217): array of shape (4,) + Jac.shape[:-2]."""
+    return _lib.phys_props_from_jac(Jac, refangle=refangle, refscale=refscale, diff=diff, poisson_ratio=poisson_ratio,
+                                    dtype=_dt(dtype))
+
+
+# ---- Kerelsky decomposition (property_extract.py:457-479, :696-883)----------------------------------------------------------
 KERELSKY_DELTA = 0.16          # Poisson ratio of the strain matrix, as calc_abcd's delta (property_extract.py:511)
 
 
