@@ -1,5 +1,6 @@
 // C ABI: per-pixel Kerelsky fits (pyGPA/property_extract.py:780-883), kernel in gpa_kerelsky.hip, arithmetic in gpa_kerelsky.h.
-// Needs no plan.  Every argument is checked, and named in the error, before a device is touched.
+// Needs no plan: the host-pointer form stages in one DevBuf of its own (gpa_hoststage.h) that goes when the call returns.
+// Every argument is checked, and named in the error, before a device is touched.
 #include "gpa_plan.h"
 #include "gpa_kerelsky.h"
 
@@ -51,17 +52,13 @@ int gpa_kerelsky_fit(int device, int dtype, size_t npx, const void* jac, const d
                      double retry_cost, void* out, double* cost) {
   TRY(kerelsky_check("gpa_kerelsky_fit", dtype, npx, jac, a0, x0, max_nfev, retry_cost, out));
   if (npx == 0) return GPA_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(GPA_ERR_NODEV, "gpa_kerelsky_fit: no HIP device");
-  HIP_TRY(hipSetDevice(device));
-  const size_t bytes = 4 * npx * (dtype == GPA_F32 ? 4 : 8);
-  DevBuf d_j, d_x, d_c;   // temporaries of this call
-  HIP_TRY(d_j.reserve(bytes, nullptr));
-  HIP_TRY(d_x.reserve(bytes, nullptr));
-  if (cost) HIP_TRY(d_c.reserve(npx * sizeof(double), nullptr));
-  HIP_TRY(hipMemcpy(d_j.ptr, jac, bytes, hipMemcpyHostToDevice));
-  HIP_TRY(launch_kerelsky(dtype, d_j.ptr, npx, pack(a0, x0, max_nfev, retry_cost), d_x.ptr, cost ? d_c.as<double>() : nullptr, nullptr));
-  HIP_TRY(hipMemcpy(out, d_x.ptr, bytes, hipMemcpyDeviceToHost));
-  if (cost) HIP_TRY(hipMemcpy(cost, d_c.ptr, npx * sizeof(double), hipMemcpyDeviceToHost));
+  TRY(need_device("gpa_kerelsky_fit", device));
+  const size_t bytes = 4 * npx * dtype_size(dtype);
+  DevBuf tmp;   // a temporary of this call
+  HostStage st(tmp, nullptr);
+  const int i_jac = st.in(jac, bytes), i_out = st.out(out, bytes), i_cost = st.out(cost, npx * sizeof(double));
+  HIP_TRY(st.upload());
+  HIP_TRY(launch_kerelsky(dtype, st.dev(i_jac), npx, pack(a0, x0, max_nfev, retry_cost), st.dev(i_out), st.as<double>(i_cost), nullptr));
+  HIP_TRY(st.download());
   return GPA_OK;
 }

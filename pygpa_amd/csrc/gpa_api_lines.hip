@@ -1,9 +1,9 @@
 // C ABI: per-line medians and homogenize_per_axis (pyGPA/imagetools.py:112-125), kernels in gpa_lines.hip, keys, ranks and
 // limits in gpa_lines.h.
 //
-// Every argument is checked before a device is touched.  All work space is the plan's (gpa_plan::lines, ::lines_tab,
-// ::lines_stage), so gpa_plan_workspace_bytes counts it.  The taps are built in f64 exactly as scipy.ndimage builds them and kept
-// for the last sigma: a repeated call with the same sigma uploads nothing and does not synchronise.
+// Every argument is checked before a device is touched.  All work space is the plan's (gpa_plan::lines, ::lines_tab; the
+// host-pointer forms stage in gpa_plan::host_stage), so gpa_plan_workspace_bytes counts it.  The taps are built in f64 exactly as
+// scipy.ndimage builds them and kept for the last sigma: a repeated call with the same sigma uploads nothing and does not synchronise.
 //
 // One homogenisation of nb frames:  transpose (mask applied) -> column medians -> profile 0, q0 -> row medians of image / q0
 // (mask and division applied as the rows are loaded: `res` after axis 0 is never stored) -> profile 1, q1 -> out = (image / q0) / q1.
@@ -13,8 +13,6 @@
 static_assert(GPA_LINES_MAX_N == LINES_MAX_N, "the limit of gpa_hip.h is that of gpa_lines.h");
 
 namespace {
-
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // the plan's work buffer for nb frames: nb transposed planes, then per frame three lines of n1 + n0 reals -- the reduced lines
 // (axis 0: n1 values, then axis 1: n0 values), the filtered profiles and the divisors q
@@ -115,8 +113,7 @@ int homogenize_checked(gpa_plan* p, const void* image, const uint8_t* mask, doub
   LINES_TRY(who, lines_apply(p->dtype, image, w.q, w.stride, w.q + off1, w.stride, out, p->n0, p->n1, nb, p->stream));
   if (profiles)
     HIP_TRY(hipMemcpyAsync(profiles, w.prof, (size_t)nb * w.stride * rsz, hipMemcpyDeviceToDevice, p->stream));
-  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
-  return GPA_OK;
+  return prof_finish(p);
 }
 
 // one frame with the reduced lines given: line0 (n1 values), line1 (n0 values, nullable: out = image / q0)
@@ -135,14 +132,7 @@ int homogenize_lines_checked(gpa_plan* p, const void* image, double sigma, const
   LINES_TRY(who, lines_apply(p->dtype, image, w.q, 0, line1 ? w.q + off1 : nullptr, 0, out, p->n0, p->n1, 1, p->stream));
   if (profiles)
     HIP_TRY(hipMemcpyAsync(profiles, w.prof, ((size_t)p->n1 + (line1 ? p->n0 : 0)) * rsz, hipMemcpyDeviceToDevice, p->stream));
-  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
-  return GPA_OK;
-}
-
-int stage(gpa_plan* p, size_t bytes, unsigned char** base) {
-  TRY(plan_reserve(p, p->lines_stage, bytes, "hipMalloc"));
-  *base = p->lines_stage.as<unsigned char>();
-  return GPA_OK;
+  return prof_finish(p);
 }
 
 }  // namespace
@@ -155,23 +145,19 @@ int gpa_line_nanmedian_dev(gpa_plan* p, const void* image_dev, const uint8_t* ma
   TRY(lines_work(p, 1, axis == 0, &w));
   ProfInstall prof(p);
   LINES_TRY(who, lines_median(p->dtype, image_dev, mask_dev, p->n0, p->n1, 1, axis, propagate_nan != 0, nullptr, 0, w.tws, out_dev, 0, p->stream));
-  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
-  return GPA_OK;
+  return prof_finish(p);
 }
 
 int gpa_line_nanmedian(gpa_plan* p, const void* image, const uint8_t* mask, int axis, int propagate_nan, void* out) {
   TRY(median_check(p, image, axis, out, "gpa_line_nanmedian"));
   HIP_TRY(hipSetDevice(p->device));
-  const size_t npx = (size_t)p->n0 * p->n1, pr = up256(npx * p->rsz), pb = up256(npx);
-  const size_t nout = (size_t)(axis == 0 ? p->n1 : p->n0) * p->rsz;
-  unsigned char* b = nullptr;
-  TRY(stage(p, pr + pb + up256(nout), &b));
-  unsigned char *d_img = b, *d_mask = b + pr, *d_out = b + pr + pb;
-  HIP_TRY(hipMemcpyAsync(d_img, image, npx * p->rsz, hipMemcpyHostToDevice, p->stream));
-  if (mask) HIP_TRY(hipMemcpyAsync(d_mask, mask, npx, hipMemcpyHostToDevice, p->stream));
-  TRY(gpa_line_nanmedian_dev(p, d_img, mask ? d_mask : nullptr, axis, propagate_nan, d_out));
-  HIP_TRY(hipMemcpyAsync(out, d_out, nout, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  const size_t npx = (size_t)p->n0 * p->n1;
+  HostStage st(p->host_stage, p->stream);
+  const int i_img = st.in(image, npx * p->rsz), i_mask = st.in(mask, npx);
+  const int i_out = st.out(out, (size_t)(axis == 0 ? p->n1 : p->n0) * p->rsz);
+  HIP_TRY(st.upload());
+  TRY(gpa_line_nanmedian_dev(p, st.dev(i_img), st.as<uint8_t>(i_mask), axis, propagate_nan, st.dev(i_out)));
+  HIP_TRY(st.download());
   return GPA_OK;
 }
 
@@ -185,17 +171,13 @@ int gpa_homogenize_per_axis(gpa_plan* p, const void* image, const uint8_t* mask,
                             void* profiles) {
   TRY(homogenize_check(p, image, sigma, nb, out, "gpa_homogenize_per_axis"));
   HIP_TRY(hipSetDevice(p->device));
-  const size_t npx = (size_t)p->n0 * p->n1, frames = (size_t)nb * npx * p->rsz, pr = up256(frames), pb = up256(npx);
-  const size_t lines = (size_t)nb * ((size_t)p->n0 + p->n1) * p->rsz;
-  unsigned char* b = nullptr;
-  TRY(stage(p, 2 * pr + pb + up256(lines), &b));
-  unsigned char *d_img = b, *d_out = b + pr, *d_mask = b + 2 * pr, *d_prof = b + 2 * pr + pb;
-  HIP_TRY(hipMemcpyAsync(d_img, image, frames, hipMemcpyHostToDevice, p->stream));
-  if (mask) HIP_TRY(hipMemcpyAsync(d_mask, mask, npx, hipMemcpyHostToDevice, p->stream));
-  TRY(homogenize_checked(p, d_img, mask ? d_mask : nullptr, sigma, propagate_nan != 0, nb, d_out, profiles ? d_prof : nullptr));
-  HIP_TRY(hipMemcpyAsync(out, d_out, frames, hipMemcpyDeviceToHost, p->stream));
-  if (profiles) HIP_TRY(hipMemcpyAsync(profiles, d_prof, lines, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  const size_t npx = (size_t)p->n0 * p->n1, frames = (size_t)nb * npx * p->rsz;
+  HostStage st(p->host_stage, p->stream);
+  const int i_img = st.in(image, frames), i_out = st.out(out, frames), i_mask = st.in(mask, npx);
+  const int i_prof = st.out(profiles, (size_t)nb * ((size_t)p->n0 + p->n1) * p->rsz);
+  HIP_TRY(st.upload());
+  TRY(homogenize_checked(p, st.dev(i_img), st.as<uint8_t>(i_mask), sigma, propagate_nan != 0, nb, st.dev(i_out), st.dev(i_prof)));
+  HIP_TRY(st.download());
   return GPA_OK;
 }
 
@@ -210,16 +192,12 @@ int gpa_homogenize_lines(gpa_plan* p, const void* image, double sigma, const voi
   TRY(homogenize_check(p, image, sigma, 1, out, "gpa_homogenize_lines"));
   if (!line0) return fail(GPA_ERR_ARG, "gpa_homogenize_lines: null line0");
   HIP_TRY(hipSetDevice(p->device));
-  const size_t npx = (size_t)p->n0 * p->n1, pr = up256(npx * p->rsz), l0 = (size_t)p->n1 * p->rsz, l1 = (size_t)p->n0 * p->rsz;
-  unsigned char* b = nullptr;
-  TRY(stage(p, 2 * pr + 2 * up256(l0) + 2 * up256(l1), &b));
-  unsigned char *d_img = b, *d_out = b + pr, *d_l0 = b + 2 * pr, *d_l1 = d_l0 + up256(l0), *d_prof = d_l1 + up256(l1);
-  HIP_TRY(hipMemcpyAsync(d_img, image, npx * p->rsz, hipMemcpyHostToDevice, p->stream));
-  HIP_TRY(hipMemcpyAsync(d_l0, line0, l0, hipMemcpyHostToDevice, p->stream));
-  if (line1) HIP_TRY(hipMemcpyAsync(d_l1, line1, l1, hipMemcpyHostToDevice, p->stream));
-  TRY(homogenize_lines_checked(p, d_img, sigma, d_l0, line1 ? d_l1 : nullptr, d_out, profiles ? d_prof : nullptr));
-  HIP_TRY(hipMemcpyAsync(out, d_out, npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
-  if (profiles) HIP_TRY(hipMemcpyAsync(profiles, d_prof, l0 + (line1 ? l1 : 0), hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  const size_t plane = (size_t)p->n0 * p->n1 * p->rsz, l0 = (size_t)p->n1 * p->rsz, l1 = (size_t)p->n0 * p->rsz;
+  HostStage st(p->host_stage, p->stream);
+  const int i_img = st.in(image, plane), i_out = st.out(out, plane), i_l0 = st.in(line0, l0), i_l1 = st.in(line1, l1);
+  const int i_prof = st.out(profiles, l0 + (line1 ? l1 : 0));
+  HIP_TRY(st.upload());
+  TRY(homogenize_lines_checked(p, st.dev(i_img), sigma, st.dev(i_l0), st.dev(i_l1), st.dev(i_out), st.dev(i_prof)));
+  HIP_TRY(st.download());
   return GPA_OK;
 }

@@ -1,7 +1,7 @@
 // C ABI: image preparation (pyGPA/imagetools.py:92-194), kernels in gpa_prep.hip, geometry and limits in gpa_prep.h.
 //
-// Every argument is checked before a device is touched.  All work space is the plan's (gpa_plan::prep, ::prep_tab,
-// ::prep_stage), so gpa_plan_workspace_bytes counts it.  The filter tables (transfer functions and twiddles of the two segment
+// Every argument is checked before a device is touched.  All work space is the plan's (gpa_plan::prep, ::prep_tab; the
+// host-pointer forms stage in gpa_plan::host_stage), so gpa_plan_workspace_bytes counts it.  The filter tables (transfer functions and twiddles of the two segment
 // lengths, or the taps of the direct route) are built in f64, rounded once and kept for the last sigma: a repeated call with
 // the same sigma uploads nothing and does not synchronise.
 #include "gpa_plan.h"
@@ -10,8 +10,6 @@
 static_assert(GPA_PREP_MAX_R == PREP_MAX_R && GPA_PREP_MAX_N1 == PREP_MAX_N1, "the limits of gpa_hip.h are those of gpa_prep.h");
 
 namespace {
-
-size_t up256(size_t b) { return (b + 255) & ~(size_t)255; }
 
 // the plan's work buffer: [0, 16) min / max keys, [64, 80) lims, [256, 768) chords, from 1024 on two real planes and two byte planes
 struct PrepWork {
@@ -127,8 +125,7 @@ int homogenize_checked(gpa_plan* p, const void* image, const void* mask, double 
   ProfInstall prof(p);
   const hipError_t e = prep_homogenize(p->dtype, a, p->stream);
   if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_gauss_homogenize: ") + hipGetErrorString(e));
-  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
-  return GPA_OK;
+  return prof_finish(p);
 }
 
 int erode_check(const gpa_plan* p, const void* in, int r, const void* out, const char* who) {
@@ -160,8 +157,7 @@ int erode_checked(gpa_plan* p, const void* in, int invert, int r, void* out) {
   const hipError_t e = prep_erode_disk(static_cast<const uint8_t*>(in), invert != 0, r, p->n0, p->n1, w.cov0, w.chord,
                                        static_cast<uint8_t*>(out), p->stream);
   if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_mask_erode_disk: ") + hipGetErrorString(e));
-  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
-  return GPA_OK;
+  return prof_finish(p);
 }
 
 int any_equal_check(const gpa_plan* p, const void* frames, int B, const void* hit, const char* who) {
@@ -170,13 +166,6 @@ int any_equal_check(const gpa_plan* p, const void* frames, int B, const void* hi
   if (!frames) return fail(GPA_ERR_ARG, w + "null frames");
   if (!hit) return fail(GPA_ERR_ARG, w + "null hit");
   if (B < 1) return fail(GPA_ERR_ARG, w + "need B >= 1 (B = " + std::to_string(B) + ")");
-  return GPA_OK;
-}
-
-// device staging of the host-pointer forms
-int stage(gpa_plan* p, size_t bytes, unsigned char** base) {
-  TRY(plan_reserve(p, p->prep_stage, bytes, "hipMalloc"));
-  *base = p->prep_stage.as<unsigned char>();
   return GPA_OK;
 }
 
@@ -194,16 +183,13 @@ int gpa_gauss_homogenize(gpa_plan* p, const void* image, const uint8_t* mask, do
   int R = 0, lg0 = 0, lg1 = 0;
   TRY(homogenize_check(p, image, mask, sigma, out, "gpa_gauss_homogenize", &R, &lg0, &lg1));
   HIP_TRY(hipSetDevice(p->device));
-  const size_t npx = (size_t)p->n0 * p->n1, pr = up256(npx * p->rsz), pb = up256(npx);
-  unsigned char* b = nullptr;
-  TRY(stage(p, 3 * pr + pb, &b));
-  unsigned char *d_img = b, *d_out = b + pr, *d_vv = b + 2 * pr, *d_mask = b + 3 * pr;
-  HIP_TRY(hipMemcpyAsync(d_img, image, npx * p->rsz, hipMemcpyHostToDevice, p->stream));
-  HIP_TRY(hipMemcpyAsync(d_mask, mask, npx, hipMemcpyHostToDevice, p->stream));
-  TRY(homogenize_checked(p, d_img, d_mask, sigma, R, lg0, lg1, use_nan_scale, nan_scale, d_out, vv_out ? d_vv : nullptr));
-  HIP_TRY(hipMemcpyAsync(out, d_out, npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
-  if (vv_out) HIP_TRY(hipMemcpyAsync(vv_out, d_vv, npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  const size_t npx = (size_t)p->n0 * p->n1;
+  HostStage st(p->host_stage, p->stream);
+  const int i_img = st.in(image, npx * p->rsz), i_out = st.out(out, npx * p->rsz), i_vv = st.out(vv_out, npx * p->rsz);
+  const int i_mask = st.in(mask, npx);
+  HIP_TRY(st.upload());
+  TRY(homogenize_checked(p, st.dev(i_img), st.dev(i_mask), sigma, R, lg0, lg1, use_nan_scale, nan_scale, st.dev(i_out), st.dev(i_vv)));
+  HIP_TRY(st.download());
   return GPA_OK;
 }
 
@@ -213,21 +199,18 @@ int gpa_mask_any_equal_dev(gpa_plan* p, const void* frames_dev, int B, double va
   ProfInstall prof(p);
   const hipError_t e = prep_any_equal(p->dtype, frames_dev, B, p->n0, p->n1, value, accumulate != 0, hit_dev, p->stream);
   if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_mask_any_equal: ") + hipGetErrorString(e));
-  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
-  return GPA_OK;
+  return prof_finish(p);
 }
 
 int gpa_mask_any_equal(gpa_plan* p, const void* frames, int B, double value, int accumulate, uint8_t* hit) {
   TRY(any_equal_check(p, frames, B, hit, "gpa_mask_any_equal"));
   HIP_TRY(hipSetDevice(p->device));
-  const size_t npx = (size_t)p->n0 * p->n1, pb = up256(npx);
-  unsigned char* b = nullptr;
-  TRY(stage(p, pb + (size_t)B * npx * p->rsz, &b));
-  if (accumulate) HIP_TRY(hipMemcpyAsync(b, hit, npx, hipMemcpyHostToDevice, p->stream));
-  HIP_TRY(hipMemcpyAsync(b + pb, frames, (size_t)B * npx * p->rsz, hipMemcpyHostToDevice, p->stream));
-  TRY(gpa_mask_any_equal_dev(p, b + pb, B, value, accumulate, b));
-  HIP_TRY(hipMemcpyAsync(hit, b, npx, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  const size_t npx = (size_t)p->n0 * p->n1;
+  HostStage st(p->host_stage, p->stream);
+  const int i_hit = st.inout(hit, npx, accumulate != 0), i_frames = st.in(frames, (size_t)B * npx * p->rsz);
+  HIP_TRY(st.upload());
+  TRY(gpa_mask_any_equal_dev(p, st.dev(i_frames), B, value, accumulate, st.as<uint8_t>(i_hit)));
+  HIP_TRY(st.download());
   return GPA_OK;
 }
 
@@ -239,13 +222,12 @@ int gpa_mask_erode_disk_dev(gpa_plan* p, const uint8_t* in_dev, int invert, int 
 int gpa_mask_erode_disk(gpa_plan* p, const uint8_t* in, int invert, int r, uint8_t* out) {
   TRY(erode_check(p, in, r, out, "gpa_mask_erode_disk"));
   HIP_TRY(hipSetDevice(p->device));
-  const size_t npx = (size_t)p->n0 * p->n1, pb = up256(npx);
-  unsigned char* b = nullptr;
-  TRY(stage(p, 2 * pb, &b));
-  HIP_TRY(hipMemcpyAsync(b, in, npx, hipMemcpyHostToDevice, p->stream));
-  TRY(erode_checked(p, b, invert, r, b + pb));
-  HIP_TRY(hipMemcpyAsync(out, b + pb, npx, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  const size_t npx = (size_t)p->n0 * p->n1;
+  HostStage st(p->host_stage, p->stream);
+  const int i_in = st.in(in, npx), i_out = st.out(out, npx);
+  HIP_TRY(st.upload());
+  TRY(erode_checked(p, st.dev(i_in), invert, r, st.dev(i_out)));
+  HIP_TRY(st.download());
   return GPA_OK;
 }
 
@@ -269,11 +251,10 @@ int gpa_mask_bounds(gpa_plan* p, const uint8_t* mask, int32_t* lims) {
   if (!mask) return fail(GPA_ERR_ARG, w + "null mask");
   if (!lims) return fail(GPA_ERR_ARG, w + "null lims");
   HIP_TRY(hipSetDevice(p->device));
-  const size_t npx = (size_t)p->n0 * p->n1;
-  unsigned char* b = nullptr;
-  TRY(stage(p, npx, &b));
-  HIP_TRY(hipMemcpyAsync(b, mask, npx, hipMemcpyHostToDevice, p->stream));
-  return gpa_mask_bounds_dev(p, b, lims);
+  HostStage st(p->host_stage, p->stream);
+  const int i_mask = st.in(mask, (size_t)p->n0 * p->n1);
+  HIP_TRY(st.upload());
+  return gpa_mask_bounds_dev(p, st.as<uint8_t>(i_mask), lims);   // (drains the stream)
 }
 
 int gpa_nan_lines_dev(gpa_plan* p, const void* image_dev, uint8_t* rows, uint8_t* cols) {
@@ -301,11 +282,10 @@ int gpa_nan_lines(gpa_plan* p, const void* image, uint8_t* rows, uint8_t* cols) 
   if (!rows) return fail(GPA_ERR_ARG, w + "null rows");
   if (!cols) return fail(GPA_ERR_ARG, w + "null cols");
   HIP_TRY(hipSetDevice(p->device));
-  const size_t bytes = (size_t)p->n0 * p->n1 * p->rsz;
-  unsigned char* b = nullptr;
-  TRY(stage(p, bytes, &b));
-  HIP_TRY(hipMemcpyAsync(b, image, bytes, hipMemcpyHostToDevice, p->stream));
-  return gpa_nan_lines_dev(p, b, rows, cols);
+  HostStage st(p->host_stage, p->stream);
+  const int i_img = st.in(image, (size_t)p->n0 * p->n1 * p->rsz);
+  HIP_TRY(st.upload());
+  return gpa_nan_lines_dev(p, st.dev(i_img), rows, cols);   // (drains the stream)
 }
 
 int gpa_nan_trim_lims_dev(gpa_plan* p, const void* image_dev, int32_t* lims) {
@@ -328,9 +308,8 @@ int gpa_nan_trim_lims(gpa_plan* p, const void* image, int32_t* lims) {
   if (!image) return fail(GPA_ERR_ARG, w + "null image");
   if (!lims) return fail(GPA_ERR_ARG, w + "null lims");
   HIP_TRY(hipSetDevice(p->device));
-  const size_t bytes = (size_t)p->n0 * p->n1 * p->rsz;
-  unsigned char* b = nullptr;
-  TRY(stage(p, bytes, &b));
-  HIP_TRY(hipMemcpyAsync(b, image, bytes, hipMemcpyHostToDevice, p->stream));
-  return gpa_nan_trim_lims_dev(p, b, lims);
+  HostStage st(p->host_stage, p->stream);
+  const int i_img = st.in(image, (size_t)p->n0 * p->n1 * p->rsz);
+  HIP_TRY(st.upload());
+  return gpa_nan_trim_lims_dev(p, st.dev(i_img), lims);   // (drains the stream)
 }

@@ -50,8 +50,7 @@ int gpa_per_dft_dev(gpa_plan* p, const void* d_image, void* d_out) {
   ProfInstall prof(p);
   TRY(per_dft_staged(p, d_image, nullptr));
   HIP_TRY(hipMemcpyAsync(d_out, p->d_lockin, (size_t)p->n0 * p->n1 * p->csz, hipMemcpyDeviceToDevice, p->stream));
-  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
-  return GPA_OK;
+  return prof_finish(p);
 }
 
 int gpa_per_dft(gpa_plan* p, const void* image, void* out) {
@@ -291,8 +290,7 @@ int gpa_phasegradient2J_dev(gpa_plan* p, const double* kvecs, int P, const void*
   for (int i = 0; i < 2 * P; ++i) kiso[i] = kvecs[i] + (dks ? dks[i] : 0.0);
   TRY(stage_kmat(p, kiso, P));
   HIP_TRY(launch_jacobian(p->dtype, grads, weights, p->d_kmat, P, (size_t)p->n0 * p->n1, nmperpixel, dks, J, p->stream));
-  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
-  return GPA_OK;
+  return prof_finish(p);
 }
 
 // weights of the lock-ins as the reference's callers form them, np.abs(g['lockin']) (P x n0 x n1 complex -> P x n0 x n1 real)
@@ -302,8 +300,7 @@ int gpa_lockin_weights_dev(gpa_plan* p, const void* lockins, int P, void* weight
   HIP_TRY(hipSetDevice(p->device));
   ProfInstall prof(p);
   HIP_TRY(launch_cabs(p->dtype, lockins, (size_t)P * p->n0 * p->n1, weights, p->stream));
-  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
-  return GPA_OK;
+  return prof_finish(p);
 }
 
 int gpa_phasegradient2J(gpa_plan* p, const double* kvecs, int P, const void* grads, const void* weights,
@@ -338,16 +335,14 @@ int gpa_props_from_jac(int device, int dtype, size_t npx, const void* jac, int a
   if (!jac || !props) return fail(GPA_ERR_ARG, "gpa_props_from_jac: null argument");
   if (dtype != GPA_F32 && dtype != GPA_F64) return fail(GPA_ERR_ARG, "gpa_props_from_jac: dtype must be GPA_F32 or GPA_F64");
   if (npx == 0) return GPA_OK;
-  int ndev = 0;
-  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(GPA_ERR_NODEV, "gpa_props_from_jac: no HIP device");
-  HIP_TRY(hipSetDevice(device));
-  const size_t bytes = 4 * npx * (dtype == GPA_F32 ? 4 : 8);
-  DevBuf d_j, d_p;   // temporaries of this call
-  HIP_TRY(d_j.reserve(bytes, nullptr));
-  HIP_TRY(d_p.reserve(bytes, nullptr));
-  HIP_TRY(hipMemcpy(d_j.ptr, jac, bytes, hipMemcpyHostToDevice));
-  TRY(gpa_props_from_jac_dev(device, dtype, npx, d_j.ptr, add_identity, refangle, refscale, diff, d_p.ptr, nullptr));
-  HIP_TRY(hipMemcpy(props, d_p.ptr, bytes, hipMemcpyDeviceToHost));
+  TRY(need_device("gpa_props_from_jac", device));
+  const size_t bytes = 4 * npx * dtype_size(dtype);
+  DevBuf tmp;   // a temporary of this call
+  HostStage st(tmp, nullptr);
+  const int i_jac = st.in(jac, bytes), i_props = st.out(props, bytes);
+  HIP_TRY(st.upload());
+  TRY(gpa_props_from_jac_dev(device, dtype, npx, st.dev(i_jac), add_identity, refangle, refscale, diff, st.dev(i_props), nullptr));
+  HIP_TRY(st.download());
   return GPA_OK;
 }
 

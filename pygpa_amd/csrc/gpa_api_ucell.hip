@@ -1,7 +1,8 @@
 // C ABI: unit-cell averaging and expansion (unit_cell_averaging.py:132-251), kernels in gpa_ucell.hip.
 //
 // The _dev entry points take device pointers and enqueue on the plan's stream without a host synchronisation (the
-// scratch grows with one, the first time a shape or cell needs more); the host-pointer ones are these plus the copies.
+// scratch grows with one, the first time a shape or cell needs more); the host-pointer ones are these plus the copies: the
+// plan-shaped operands in the plan's own d_image / d_u / d_wnorm, the cell-shaped ones in gpa_plan::host_stage.
 #include "gpa_plan.h"
 
 static int check_geom(const gpa_plan* p, const gpa_ucell_geom* gg, const char* who, UcellGeom* g) {
@@ -38,8 +39,7 @@ int gpa_unit_cell_average_batch_dev(gpa_plan* p, const void* images_dev, int B, 
   ProfInstall prof(p);
   const hipError_t e = ucell_average(p->dtype, images_dev, B, u_dev, p->n0, p->n1, g, res_dev, weights_dev, p->stream, &p->ucell);
   if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_unit_cell_average: ") + hipGetErrorString(e));
-  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
-  return GPA_OK;
+  return prof_finish(p);
 }
 
 int gpa_unit_cell_average_dev(gpa_plan* p, const void* image_dev, const void* u_dev, const gpa_ucell_geom* geom, double* res_dev,
@@ -52,15 +52,13 @@ int gpa_unit_cell_average(gpa_plan* p, const void* image, const void* u, const g
   UcellGeom g;
   TRY(check_geom(p, geom, "gpa_unit_cell_average", &g));
   HIP_TRY(hipSetDevice(p->device));
-  const size_t npx = (size_t)p->n0 * p->n1, ncell = (size_t)g.rs0 * g.rs1;
-  HIP_TRY(hipMemcpyAsync(p->d_image, image, npx * p->rsz, hipMemcpyHostToDevice, p->stream));
-  if (u) HIP_TRY(hipMemcpyAsync(p->d_u, u, 2 * npx * p->rsz, hipMemcpyHostToDevice, p->stream));
-  HIP_TRY(p->ucell.stage.reserve(2 * ncell * sizeof(double), p->stream));
-  double* d_out = p->ucell.stage.as<double>();
-  TRY(gpa_unit_cell_average_dev(p, p->d_image, u ? p->d_u : nullptr, geom, d_out, weights ? d_out + ncell : nullptr));
-  HIP_TRY(hipMemcpyAsync(res, d_out, ncell * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-  if (weights) HIP_TRY(hipMemcpyAsync(weights, d_out + ncell, ncell * sizeof(double), hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  const size_t plane = (size_t)p->n0 * p->n1 * p->rsz, cell = (size_t)g.rs0 * g.rs1 * sizeof(double);
+  HostStage st(p->host_stage, p->stream, sizeof(double));   // res | weights back to back, as the plan has always counted them
+  const int i_img = st.in(image, plane, p->d_image), i_u = st.in(u, 2 * plane, p->d_u);
+  const int i_res = st.out(res, cell), i_w = st.out(weights, cell);
+  HIP_TRY(st.upload());
+  TRY(gpa_unit_cell_average_dev(p, st.dev(i_img), st.dev(i_u), geom, st.as<double>(i_res), st.as<double>(i_w)));
+  HIP_TRY(st.download());
   return GPA_OK;
 }
 
@@ -74,8 +72,7 @@ int gpa_expand_unitcell_dev(gpa_plan* p, const double* cell_dev, const gpa_ucell
   ProfInstall prof(p);
   const hipError_t e = ucell_expand(p->dtype, cell_dev, g, z2, u_dev, p->n0, p->n1, out_dev, p->stream, &p->ucell);
   if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_expand_unitcell: ") + hipGetErrorString(e));
-  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
-  return GPA_OK;
+  return prof_finish(p);
 }
 
 int gpa_expand_unitcell(gpa_plan* p, const double* cell, const gpa_ucell_geom* geom, double z2, const void* u, void* out) {
@@ -83,14 +80,12 @@ int gpa_expand_unitcell(gpa_plan* p, const double* cell, const gpa_ucell_geom* g
   UcellGeom g;
   TRY(check_geom(p, geom, "gpa_expand_unitcell", &g));
   HIP_TRY(hipSetDevice(p->device));
-  const size_t npx = (size_t)p->n0 * p->n1, ncell = (size_t)g.rs0 * g.rs1;
-  HIP_TRY(p->ucell.stage.reserve(ncell * sizeof(double), p->stream));
-  double* d_cell = p->ucell.stage.as<double>();
-  void* d_out = p->d_wnorm;   // (n0 x n1 reals of the plan)
-  HIP_TRY(hipMemcpyAsync(d_cell, cell, ncell * sizeof(double), hipMemcpyHostToDevice, p->stream));
-  if (u) HIP_TRY(hipMemcpyAsync(p->d_u, u, 2 * npx * p->rsz, hipMemcpyHostToDevice, p->stream));
-  TRY(gpa_expand_unitcell_dev(p, d_cell, geom, z2, u ? p->d_u : nullptr, d_out));
-  HIP_TRY(hipMemcpyAsync(out, d_out, npx * p->rsz, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  const size_t plane = (size_t)p->n0 * p->n1 * p->rsz;
+  HostStage st(p->host_stage, p->stream);
+  const int i_cell = st.in(cell, (size_t)g.rs0 * g.rs1 * sizeof(double)), i_u = st.in(u, 2 * plane, p->d_u);
+  const int i_out = st.out(out, plane, p->d_wnorm);   // (n0 x n1 reals of the plan)
+  HIP_TRY(st.upload());
+  TRY(gpa_expand_unitcell_dev(p, st.as<double>(i_cell), geom, z2, st.dev(i_u), st.dev(i_out)));
+  HIP_TRY(st.download());
   return GPA_OK;
 }

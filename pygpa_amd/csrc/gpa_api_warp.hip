@@ -40,8 +40,7 @@ int gpa_invert_u_mode_dev(gpa_plan* p, const void* u_dev, double scale, int iter
   const hipError_t e = overlap ? warp_invert_u(p->dtype, u_dev, p->n0, p->n1, scale, iters, edge, 0, out_dev, p->stream, mode, 1, &p->warp, rects, nrect)
                                : warp_invert_u(p->dtype, u_dev, p->n0, p->n1, scale, iters, 0, edge, out_dev, p->stream, mode, 0, &p->warp, rects, nrect);
   if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_invert_u_mode_dev: ") + hipGetErrorString(e));
-  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
-  return GPA_OK;
+  return prof_finish(p);
 }
 
 // undistort_image (geometric_phase_analysis.py:935-974): u_inv = invert_u_overlap(-u) (35 rounds, mode 'nearest', no
@@ -66,8 +65,7 @@ int gpa_undistort_image_scaled_dev(gpa_plan* p, const void* deformed_dev, const 
   void* uinv = uinv_dev ? uinv_dev : p->d_dudx;   // (2 planes of n0 x n1 fit)
   HIP_TRY(warp_invert_u(p->dtype, u_dev, p->n0, p->n1, -scale, 35, 0, 0, uinv, p->stream, 0, 1, &p->warp, rects, nrect));
   HIP_TRY(warp_image(p->dtype, deformed_dev, uinv, p->n0, p->n1, out_dev, p->stream, &p->warp, rects, nrect));
-  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
-  return GPA_OK;
+  return prof_finish(p);
 }
 
 // undistort_image of a stack (no counterpart in the reference: a loop over undistort_image, geometric_phase_analysis.py:935-974).
@@ -87,8 +85,7 @@ int gpa_undistort_image_batch_dev(gpa_plan* p, const void* frames_dev, int B, co
   ProfInstall prof(p);
   void* uinv = uinv_dev ? uinv_dev : (u_per_frame ? nullptr : p->d_dudx);   // (a shared u_inv: 2 planes of n0 x n1 fit)
   HIP_TRY(warp_undistort_stack(p->dtype, frames_dev, B, u_dev, u_per_frame ? 1 : 0, scale, uinv, p->n0, p->n1, out_dev, p->stream, &p->warp));
-  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
-  return GPA_OK;
+  return prof_finish(p);
 }
 
 // the host-pointer form: the frames are staged through device buffers of one chunk (the scratch's chunk); a shared field is

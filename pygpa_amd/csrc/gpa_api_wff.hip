@@ -2,7 +2,8 @@
 //
 // The taps are built here in f64 -- g(j) = exp(-j^2 / 2 sigma^2), kx(j) = g(j) e^(i wx j), ky(j) = g(j) e^(i wy j) / sum g^2,
 // every phasor from its own cos / sin, none by recurrence -- rounded once to the plan's precision and uploaded once per call.
-// All work space is the plan's (gpa_plan::wff, ::wff_stage), so gpa_plan_workspace_bytes counts it.
+// All work space is the plan's (gpa_plan::wff; the host-pointer form stages in gpa_plan::host_stage), so
+// gpa_plan_workspace_bytes counts it.
 #include "gpa_plan.h"
 #include "gpa_wff.h"
 
@@ -59,9 +60,9 @@ static void wff_tables(double sigma, int s, int wpad, const double* wxs, int Kx,
     g[t] = exp(-(j * j) / (2.0 * sigma * sigma));
     nrm += g[t] * g[t];
   }
-  *off_tyr = (((size_t)Kx * W * 2 * sizeof(R)) + 255) & ~(size_t)255;
-  *off_thr = (*off_tyr + (size_t)Ky * wpad * 2 * sizeof(R) + 255) & ~(size_t)255;
-  bytes.assign(*off_thr + ((TT * sizeof(R) + 255) & ~(size_t)255), 0);
+  *off_tyr = up256((size_t)Kx * W * 2 * sizeof(R));
+  *off_thr = up256(*off_tyr + (size_t)Ky * wpad * 2 * sizeof(R));
+  bytes.assign(*off_thr + up256(TT * sizeof(R)), 0);
   R* tx = reinterpret_cast<R*>(bytes.data());
   R* ty = reinterpret_cast<R*>(bytes.data() + *off_tyr);
   R* t2 = reinterpret_cast<R*>(bytes.data() + *off_thr);
@@ -93,7 +94,7 @@ static int wff_dev_checked(gpa_plan* p, const void* image_dev, double sigma, int
   size_t off_tyr = 0, off_thr = 0;
   if (f64) wff_tables<double>(sigma, s, tl.wpad, wxs, Kx, wys, Ky, thresholds, T, tab, &off_tyr, &off_thr);
   else wff_tables<float>(sigma, s, tl.wpad, wxs, Kx, wys, Ky, thresholds, T, tab, &off_tyr, &off_thr);
-  const size_t plane = ((size_t)p->n0 * p->n1 * p->csz + 255) & ~(size_t)255;
+  const size_t plane = up256((size_t)p->n0 * p->n1 * p->csz);
   TRY(plan_reserve(p, p->wff, tab.size() + (size_t)(1 + T) * plane, "hipMalloc"));
   unsigned char* base = p->wff.as<unsigned char>();
   // (pageable source: the copy has left `tab` when the stream has drained)
@@ -103,8 +104,7 @@ static int wff_dev_checked(gpa_plan* p, const void* image_dev, double sigma, int
   const hipError_t e = wff_run(p->dtype, image_dev, p->n0, p->n1, s, base, Kx, base + off_tyr, Ky, base + off_thr, T, scale,
                                base + tab.size(), base + tab.size() + plane, out_dev, p->stream);
   if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("gpa_wff: ") + hipGetErrorString(e));
-  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
-  return GPA_OK;
+  return prof_finish(p);
 }
 
 int gpa_wff_dev(gpa_plan* p, const void* image_dev, double sigma, const double* wxs, int Kx, const double* wys, int Ky,
@@ -119,13 +119,11 @@ int gpa_wff(gpa_plan* p, const void* image, double sigma, const double* wxs, int
   int s = 0;
   TRY(wff_check(p, image, sigma, wxs, Kx, wys, Ky, thresholds, T, scale, out, "gpa_wff", &s));
   HIP_TRY(hipSetDevice(p->device));
-  const size_t npx = (size_t)p->n0 * p->n1, plane = (npx * p->csz + 255) & ~(size_t)255;
-  TRY(plan_reserve(p, p->wff_stage, plane + (size_t)T * npx * p->csz, "hipMalloc"));
-  unsigned char* d_img = p->wff_stage.as<unsigned char>();
-  unsigned char* d_out = d_img + plane;
-  HIP_TRY(hipMemcpyAsync(d_img, image, npx * p->csz, hipMemcpyHostToDevice, p->stream));
-  TRY(wff_dev_checked(p, d_img, sigma, s, wxs, Kx, wys, Ky, thresholds, T, scale, d_out));
-  HIP_TRY(hipMemcpyAsync(out, d_out, (size_t)T * npx * p->csz, hipMemcpyDeviceToHost, p->stream));
-  HIP_TRY(hipStreamSynchronize(p->stream));
+  const size_t plane = (size_t)p->n0 * p->n1 * p->csz;
+  HostStage st(p->host_stage, p->stream);
+  const int i_img = st.in(image, plane), i_out = st.out(out, (size_t)T * plane);
+  HIP_TRY(st.upload());
+  TRY(wff_dev_checked(p, st.dev(i_img), sigma, s, wxs, Kx, wys, Ky, thresholds, T, scale, st.dev(i_out)));
+  HIP_TRY(st.download());
   return GPA_OK;
 }

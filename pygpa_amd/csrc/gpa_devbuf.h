@@ -1,19 +1,21 @@
 // One growable buffer with one owner: device memory (or, with pinned = true, page-locked host memory) that is grown on
 // demand, reported to a byte counter and freed by its destructor.  Host-only.  Everything the plan allocates goes through it.
 //
-// The three primitives -- allocate, free, drain the stream -- are the inline functions below.  With GPA_DEVBUF_HOST_SEAM
-// defined they are malloc / free / nothing and count their calls, and the n-th allocation can be made to fail: that is how
-// tests/host/devbuf_check.cpp checks the type without a GPU.
+// The four primitives -- allocate, free, drain the stream, copy between host and device (for gpa_hoststage.h) -- are the
+// inline functions below.  With GPA_DEVBUF_HOST_SEAM defined they are malloc / free / nothing / memcpy and count their calls,
+// and the n-th allocation can be made to fail: that is how tests/host/devbuf_check.cpp and hoststage_check.cpp check the types
+// without a GPU.
 #pragma once
 #include <stddef.h>
 
 #ifdef GPA_DEVBUF_HOST_SEAM
 #include <stdlib.h>
+#include <string.h>
 typedef int hipError_t;
 typedef void* hipStream_t;
-constexpr hipError_t hipSuccess = 0, hipErrorOutOfMemory = 2;
+constexpr hipError_t hipSuccess = 0, hipErrorInvalidValue = 1, hipErrorOutOfMemory = 2;
 namespace gpa {
-struct DevBufSeam { long allocs = 0, frees = 0, syncs = 0, fail_at = 0; };   // fail_at = n > 0: the n-th allocation from now fails
+struct DevBufSeam { long allocs = 0, frees = 0, syncs = 0, fail_at = 0, copies = 0; };   // fail_at = n > 0: the n-th allocation from now fails
 inline DevBufSeam g_devbuf_seam;
 inline hipError_t devbuf_alloc(void** p, size_t bytes, bool) {
   if (g_devbuf_seam.fail_at > 0 && --g_devbuf_seam.fail_at == 0) return hipErrorOutOfMemory;
@@ -24,6 +26,11 @@ inline hipError_t devbuf_alloc(void** p, size_t bytes, bool) {
 }
 inline void devbuf_free(void* p, bool) { free(p); ++g_devbuf_seam.frees; }
 inline hipError_t devbuf_sync(hipStream_t) { ++g_devbuf_seam.syncs; return hipSuccess; }
+inline hipError_t devbuf_copy(void* dst, const void* src, size_t bytes, bool, hipStream_t) {
+  memcpy(dst, src, bytes);
+  ++g_devbuf_seam.copies;
+  return hipSuccess;
+}
 }  // namespace gpa
 #else
 #include <hip/hip_runtime.h>
@@ -31,6 +38,10 @@ namespace gpa {
 inline hipError_t devbuf_alloc(void** p, size_t bytes, bool pinned) { return pinned ? hipHostMalloc(p, bytes) : hipMalloc(p, bytes); }
 inline void devbuf_free(void* p, bool pinned) { (void)(pinned ? hipHostFree(p) : hipFree(p)); }
 inline hipError_t devbuf_sync(hipStream_t s) { return hipStreamSynchronize(s); }
+// enqueued on s; the host side must stay as it is until s has drained
+inline hipError_t devbuf_copy(void* dst, const void* src, size_t bytes, bool to_device, hipStream_t s) {
+  return hipMemcpyAsync(dst, src, bytes, to_device ? hipMemcpyHostToDevice : hipMemcpyDeviceToHost, s);
+}
 }  // namespace gpa
 #endif
 

@@ -364,7 +364,6 @@ struct UcellGeom {
 struct UcellWs {
   DevBuf buf;
   WarpWs spline{};             // prefilter taps (buf unused)
-  DevBuf stage;                // device staging of the host-pointer entry points
 };
 // frames of one batched average: gridDim.y of its sum and finish kernels
 constexpr int UCELL_MAX_FRAMES = 65535;

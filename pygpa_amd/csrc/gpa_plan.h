@@ -23,6 +23,7 @@
 #include "gpa_unwrap.h"
 #include "gpa_dft.h"
 #include "gpa_gaussfft.h"
+#include "gpa_hoststage.h"
 
 using namespace gpa;
 
@@ -222,18 +223,23 @@ struct gpa_plan {
   bool peaks_smooth_valid = false;
   WarpWs warp{};                  // scratch + taps of the Lawler-Fujita kernels (gpa_warp.hip), grown on first use
   UcellWs ucell{};                // scratch of unit-cell averaging / expansion (gpa_ucell.hip), grown on first use
-  // windowed Fourier filtering (gpa_api_wff.hip), grown on demand: tap tables, the A plane and the T planes B of a call;
-  // device staging of the host-pointer form (image, T output planes)
-  DevBuf wff{&ws_bytes}, wff_stage{&ws_bytes};
+  // Device staging of the host-pointer forms of wff, image preparation, the per-line medians and the unit-cell calls (the
+  // cell-shaped operands), laid out per call by a HostStage (gpa_hoststage.h) and grown on demand.  One buffer serves them all:
+  // every one of these forms drains the stream before it returns -- itself, or through the _dev form it tail-calls
+  // (gpa_mask_bounds, gpa_nan_lines, gpa_nan_trim_lims) -- and none calls another host form while its staged pointers are
+  // live: between upload and download they run only their own checked device path or _dev form.
+  DevBuf host_stage{&ws_bytes};
+  // windowed Fourier filtering (gpa_api_wff.hip), grown on demand: tap tables, the A plane and the T planes B of a call
+  DevBuf wff{&ws_bytes};
   // image preparation (gpa_api_prep.hip), grown on demand: the num / den planes, two byte planes, the chords and the small
-  // words of a call; the filter tables of the last (sigma, segment lengths); device staging of the host-pointer forms
-  DevBuf prep{&ws_bytes}, prep_tab{&ws_bytes}, prep_stage{&ws_bytes};
+  // words of a call; the filter tables of the last (sigma, segment lengths)
+  DevBuf prep{&ws_bytes}, prep_tab{&ws_bytes};
   double prep_sigma = -1.0;       // what prep_tab holds: sigma, the two transform lengths (0, 0: the direct route's taps)
   int prep_lg0 = -1, prep_lg1 = -1;
   int prep_chord_r = -1;          // the radius whose chords sit in prep
   // per-line medians and homogenize_per_axis (gpa_api_lines.hip), grown on demand: the transposed planes and the median /
-  // profile / divisor lines of a call; the taps of the last sigma; device staging of the host-pointer forms
-  DevBuf lines{&ws_bytes}, lines_tab{&ws_bytes}, lines_stage{&ws_bytes};
+  // profile / divisor lines of a call; the taps of the last sigma
+  DevBuf lines{&ws_bytes}, lines_tab{&ws_bytes};
   double lines_sigma = -1.0;      // the sigma whose taps sit in lines_tab
   // a8 iterate_GPA (gpa_api_iterate.hip), grown on demand: the Huber work of the batched plane fit, behind it the driver's
   // amax / psi / weight planes (and the prs / w planes of its host form)
@@ -259,7 +265,7 @@ struct gpa_plan {
   // declares the type inside its visibility pragma, which would export the two.)
   __attribute__((visibility("hidden"))) ~gpa_plan() = default;
   __attribute__((visibility("hidden"))) gpa_plan() {
-    warp.buf.counted = ucell.buf.counted = ucell.stage.counted = dftw.buf.counted = &ws_bytes;
+    warp.buf.counted = ucell.buf.counted = dftw.buf.counted = &ws_bytes;
     for (auto& ax : gft)
       for (auto& g : ax) g.H.counted = g.tw.counted = &ws_bytes;
   }
@@ -303,6 +309,19 @@ int run_passA(gpa_plan* p, const void* image, const void* mean, void* Tbuf, int 
 int passB_select(gpa_plan* p, const XPlanes& xp, int P, int K, void* lockin, int32_t* kidx, bool raw);
 int passB_phases(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, void* psi, bool* shared);
 void collect_kernel_profile(gpa_plan* p);
+// the tail of a profiled entry point: drain the stream, read the kernel events of the call
+inline int prof_finish(gpa_plan* p) {
+  if (p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }
+  return GPA_OK;
+}
+// what a plan-less host form needs before it touches a device: one to be there, and `device` selected
+inline int need_device(const char* who, int device) {
+  int ndev = 0;
+  if (hipGetDeviceCount(&ndev) != hipSuccess || ndev < 1) return fail(GPA_ERR_NODEV, std::string(who) + ": no HIP device");
+  HIP_TRY(hipSetDevice(device));
+  return GPA_OK;
+}
+inline size_t dtype_size(int dtype) { return dtype == GPA_F32 ? 4 : 8; }   // bytes of a real
 int sweep_peaks_dev(gpa_plan* p, const void* image, const void* mean, const double* krefs, int P,
                            const double* klists, int K, double sigma, void* lockin, int32_t* kidx, bool raw);
 int tile_gradients_impl(gpa_plan* p, const void* image, size_t image_pitch, int r0, int c0, bool mean_on_device,
