@@ -293,7 +293,9 @@ def weighted_lstsq(b, kmat, w):
     r1 = (ww * k1 * b).sum(0)
     det = a00 * a11 - a01 * a01
     tr = a00 + a11
-    ok = det > 1e-28 * tr * tr
+    # a determinant below its own rounding noise ((2 P + 11) / 4 round-offs of tr^2, 3.4 eps at P = 8) means rank 1;
+    # 4 eps is solve2's constant (csrc/gpa_jacmath.h).  With the earlier 1e-28 exactly rank-1 pixels divided by noise.
+    ok = det > 4 * np.finfo(np.float64).eps * tr * tr
     safe = np.where(ok, det, 1.0)
     x0 = np.where(ok, (a11 * r0 - a01 * r1) / safe, 0.0)
     x1 = np.where(ok, (a00 * r1 - a01 * r0) / safe, 0.0)

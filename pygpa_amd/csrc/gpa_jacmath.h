@@ -36,10 +36,22 @@ __device__ __forceinline__ T wrap_to_pi_fast(T x) {
   return fabs(x) < Consts<T>::two_pi ? wrap_phase_diff(x) : wrap_to_pi(x);
 }
 
+// The symmetric 2 x 2 normal system A x = r of a per-pixel weighted least-squares problem (A = M^T M, M = diag(w) K).
+// det / tr^2 is about 1 / kappa(M)^2, and the computed det carries rounding noise of up to (2 P + 11) / 4 unit round-offs of
+// tr^2 (P terms per sum; 3.4 eps at P = 8).  A determinant at that level says nothing: dividing by it returned answers of
+// any size.  Such a pixel is rank 1 to working precision and gets the minimum-norm answer along its dominant direction,
+// r / tr, which is what LAPACK's lstsq returns for an exactly rank-deficient pixel; tr = 0 (every weight 0) gives 0.
+// The test is det > 4 eps tr^2 in both precisions: 4 is the smallest power of two above the noise bound.  Measured with the
+// NumPy emulation of tools/lstsq_threshold.py (8 k-vector sets, P = 2 ... 8, 200 000 pixels each): with weights (1, r, r),
+// r = 1e-4 ... 1e-7, in f32 the answer stays within 1.000 of max(|x_lapack|, |x_rank1|) for every multiple from 2 eps on (1.2
+// at 1 eps); exactly rank-1 pixels are within 0.07 of their rounding bound from 1 eps on in both precisions.  The constants
+// used before, 1e-12 (f32) and 1e-28 (f64), lie below the noise: 13.9 times LAPACK's size at r = 1e-4 in f32, and answers
+// unrelated to LAPACK's on exactly rank-1 pixels in both precisions.  An f32 solve therefore keeps only the dominant direction
+// from kappa = 1 / sqrt(4 eps) = 1450 on, an f64 solve from 3.4e7 on ("Conditioning").
 template <class T>
 __device__ __forceinline__ void solve2(T a00, T a01, T a11, T r0, T r1, T& x0, T& x1) {
   const T det = a00 * a11 - a01 * a01, tr = a00 + a11;
-  const T tiny = sizeof(T) == 4 ? T(1e-12) : T(1e-28);
+  const T tiny = sizeof(T) == 4 ? T(4.76837158203125e-7) : T(8.8817841970012523e-16);   // 4 eps: 2^-21, 2^-50
   if (det > tiny * tr * tr) {
     const T inv = T(1) / det;
     x0 = (a11 * r0 - a01 * r1) * inv;

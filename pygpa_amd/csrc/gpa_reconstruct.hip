@@ -3,9 +3,14 @@
 // Streaming kernel, one thread per pixel.  The reference solves a P x 2 weighted
 // least-squares problem per pixel with LAPACK (myweighed_lstsq,
 // geometric_phase_analysis.py:97-113); with K = 2 pi kvecs this is the 2x2 normal
-// system (K^T W^2 K) x = K^T W^2 b, solved here in registers (min-norm answer at
-// rank-deficient pixels, 0 where every weight is 0).  MFMA has nothing to offer
-// a 3x2 problem per pixel; the kernel is HBM-bound.
+// system (K^T W^2 K) x = K^T W^2 b, solved here in registers.  A pixel whose
+// determinant is below 4 eps tr^2 -- rank 1 to working precision: all weight on one
+// direction, from a weight ratio of about 1e-3 (f32) or 5e-8 (f64) between the peaks
+// down to exactly one peak or collinear peaks -- gets the minimum-norm answer along
+// that direction, which is LAPACK's answer for an exactly rank-deficient pixel; 0
+// where every weight is 0 (solve2, gpa_jacmath.h; tests/test_gpu_lstsq.py holds every
+// kernel below to LAPACK at P = 2 ... 8).  MFMA has nothing to offer a 3x2 problem
+// per pixel; the kernel is HBM-bound.
 #include "gpa_internal.h"
 #include "gpa_jacmath.h"   // Consts, wrap_to_pi, wrap_phase_diff, wrap_to_pi_fast, solve2, Quad, lattice_props
 
