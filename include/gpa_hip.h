@@ -177,6 +177,39 @@ int gpa_unwrap(gpa_plan* plan, const void* psi, const void* weight, int kmax, do
 int gpa_unwrap_dev(gpa_plan* plan, const void* psi, const void* weight, int kmax, double eps,
                    int poisson_axes_compat, void* phi, int* iters_out);
 
+/* A stack of nb phase maps of the plan's shape, unwrapped as ONE set of kernel launches (problem = blockIdx.z): a small
+ * frame is bound by the chain of 4 - 5 dependent launches per PCG iteration, which the stack shares.  No counterpart in
+ * the reference, where a loop over phase_unwrap (phase_unwrap.py:141-208) or phase_unwrap_prediff (:282-350) gives the
+ * same numbers.  Every problem keeps its own stopping test and guards; problem b's phi and iteration count are those of
+ * gpa_unwrap_dev / gpa_unwrap_prediff_dev on its planes, bit for bit where both run the same kernels (nb <= 2, or the
+ * option NO_LAT: a single frame of up to 1024 points a side otherwise takes latency-tuned kernels that agree to rounding).
+ *   psi: nb x n0 x n1;  dx: nb x n0 x (n1 - 1), dy: nb x (n0 - 1) x n1;  phi: nb x n0 x n1, overlapping no input.
+ *   weight_planes: 0 (weight must be NULL: unweighted), 1 (one n0 x n1 plane for all problems) or nb (one plane each).
+ *   nb: 1 ... GPA_UNWRAP_BATCH_MAX.  iters_out: nb counts.
+ * A call whose work space would pass 2 GiB (option UNWRAP_STACK_BYTES=<bytes>: another bound) runs in chunks of problems
+ * inside the call, each chunk one set of launches with the kernels of the whole call: chunking changes no bit.  The work
+ * space is the plan's ONE batched unwrap workspace, shared with gpa_extract_displacement_field_batch_dev, grown to the
+ * largest need seen and counted in gpa_plan_workspace_bytes; offsets into the stack are 64-bit.
+ * _dev: device pointers on the plan's stream; iters_out == NULL only enqueues, gpa_unwrap_batch_finish then waits and
+ * hands over the nb counts of the last batch call.  The host-pointer forms stage one chunk at a time.
+ * Errors: GPA_ERR_ARG naming the argument, before anything is launched; GPA_ERR_STATE for plans without unwrap kernels
+ * and for shapes where gpa_supports_batch says 0 (loop over the single call there).
+ * gpa_unwrap_batch_problem_bytes: device bytes one problem of a kmax-iteration solve takes in that workspace (what the
+ * chunk size divides the bound by); 0 for a plan without unwrap kernels.                                               */
+#define GPA_UNWRAP_BATCH_MAX 4096
+int gpa_unwrap_batch_dev(gpa_plan* plan, const void* psi, int nb, const void* weight, int weight_planes,
+                         int kmax, double eps, int poisson_axes_compat, void* phi, int* iters_out);
+int gpa_unwrap_prediff_batch_dev(gpa_plan* plan, const void* dx, const void* dy, int nb, const void* weight,
+                                 int weight_planes, int kmax, double eps, int poisson_axes_compat, void* phi,
+                                 int* iters_out);
+int gpa_unwrap_batch_finish(gpa_plan* plan, int nb, int* iters_out);
+int gpa_unwrap_batch(gpa_plan* plan, const void* psi, int nb, const void* weight, int weight_planes,
+                     int kmax, double eps, int poisson_axes_compat, void* phi, int* iters_out);
+int gpa_unwrap_prediff_batch(gpa_plan* plan, const void* dx, const void* dy, int nb, const void* weight,
+                             int weight_planes, int kmax, double eps, int poisson_axes_compat, void* phi,
+                             int* iters_out);
+size_t gpa_unwrap_batch_problem_bytes(gpa_plan* plan, int kmax);
+
 /* fused driver: extract_displacement_field (geometric_phase_analysis.py:907-932,
  * deconvolve=False) with every intermediate kept in HBM.
  *   image : n0 x n1 (its mean is subtracted on the device, :919)

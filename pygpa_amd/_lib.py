@@ -17,6 +17,7 @@ LIB_PATH = os.environ.get('GPA_HIP_LIB') or os.path.join(_HERE, 'libgpa_hip.so')
 GPA_F32, GPA_F64 = 0, 1
 UCELL_MAX_FRAMES = 65535     # frames of one gpa_unit_cell_average_batch_dev call
 UNDISTORT_MAX_FRAMES = 65535     # frames of one gpa_undistort_image_batch[_dev] call
+UNWRAP_BATCH_MAX = 4096          # problems of one gpa_unwrap_batch[_dev] call (GPA_UNWRAP_BATCH_MAX)
 WFF_MAX_S, WFF_MAX_T = 40, 8     # half-window round(2 sigma) and thresholds of one gpa_wff[_dev] call
 PREP_MAX_R, PREP_MAX_N1 = 254, 32768     # erosion radius of gpa_mask_erode_disk, row length of gpa_gauss_homogenize
 LINES_MAX_N = 16384                      # longest line of gpa_line_nanmedian / gpa_homogenize_per_axis (GPA_LINES_MAX_N)
@@ -60,6 +61,12 @@ SIGNATURES = {
     'gpa_unwrap_finish': (_i, [_vp, _vp]),
     'gpa_unwrap': (_i, [_vp, _vp, _vp, _i, _d, _i, _vp, _vp]),
     'gpa_unwrap_dev': (_i, [_vp, _vp, _vp, _i, _d, _i, _vp, _vp]),
+    'gpa_unwrap_batch_dev': (_i, [_vp, _vp, _i, _vp, _i, _i, _d, _i, _vp, _vp]),
+    'gpa_unwrap_prediff_batch_dev': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _d, _i, _vp, _vp]),
+    'gpa_unwrap_batch_finish': (_i, [_vp, _i, _vp]),
+    'gpa_unwrap_batch': (_i, [_vp, _vp, _i, _vp, _i, _i, _d, _i, _vp, _vp]),
+    'gpa_unwrap_prediff_batch': (_i, [_vp, _vp, _vp, _i, _vp, _i, _i, _d, _i, _vp, _vp]),
+    'gpa_unwrap_batch_problem_bytes': (_sz, [_vp, _i]),
     'gpa_extract_displacement_field': (_i, [_vp, _vp, _vp, _i, _vp, _i, _d, _i, _i, _vp, _vp, _vp, _vp]),
     'gpa_extract_displacement_field_dev': (_i, [_vp, _vp, _vp, _i, _vp, _i, _d, _i, _i, _vp, _vp, _vp, _vp]),
     'gpa_extract_displacement_field_async': (_i, [_vp, _vp, _vp, _i, _vp, _i, _d, _i, _i, _vp, _vp, _vp]),
@@ -311,6 +318,38 @@ def stack_shapes(frames_shape, u_shape, plan_shape=None):
             raise ValueError('u holds %d fields for %d frames' % (u_shape[0], B))
         return B, True
     raise ValueError('u must be (2, N, M) or (B, 2, N, M) for frames (B, N, M) = %s, not %s' % (frames_shape, u_shape))
+
+
+def unwrap_stack_shapes(a_shape, dy_shape=None, plan_shape=None):
+    """B of a stack of phase maps (B, N, M) -- or, with dy_shape, of gradient pairs (B, N, M - 1) / (B, N - 1, M) -- on the
+    grid plan_shape where given; ValueError for anything else.  Pure shape arithmetic: no array, no library."""
+    a_shape = tuple(a_shape)
+    if len(a_shape) != 3:
+        raise ValueError('a stack must be three-dimensional (B, N, M), got %s' % (a_shape,))
+    if a_shape[0] < 1:
+        raise ValueError('the stack is empty')
+    if dy_shape is None:
+        grid = a_shape[1:]
+    else:
+        dy_shape = tuple(dy_shape)
+        if len(dy_shape) != 3 or dy_shape[0] != a_shape[0] or dy_shape[1] + 1 != a_shape[1] or dy_shape[2] != a_shape[2] + 1:
+            raise ValueError('dx %s and dy %s do not pair: need (B, N, M - 1) and (B, N - 1, M)' % (a_shape, dy_shape))
+        grid = (a_shape[1], dy_shape[2])
+    if grid[0] < 2 or grid[1] < 2:
+        raise ValueError('the maps must be at least 2 x 2, got %s' % (grid,))
+    if plan_shape is not None and tuple(plan_shape) != grid:
+        raise ValueError('maps of %s do not match the plan %s' % (grid, tuple(plan_shape)))
+    return a_shape[0]
+
+
+def unwrap_stack_weight_planes(w_shape, B, grid):
+    """1 for a weight (N, M) shared by the B maps of `grid`, B for (B, N, M); ValueError for anything else"""
+    w_shape, grid = tuple(w_shape), tuple(grid)
+    if w_shape == grid:
+        return 1
+    if w_shape == (B,) + grid:
+        return B
+    raise ValueError('weight must be %s or %s, got %s' % (grid, (B,) + grid, w_shape))
 
 
 class Plan:
@@ -981,6 +1020,89 @@ class Plan:
         check(self.lib.gpa_unwrap_dev(self.handle, _ptr(int(psi_ptr)), _ptr(weight_ptr), int(kmax), float(eps),
                                       1 if axes_compat else 0, _ptr(int(phi_ptr)), C.byref(iters)), 'gpa_unwrap_dev')
         return iters.value
+
+    def _stack_weight(self, weight, B):
+        """(array or None, weight_planes) of a stack call: None, one plan-shaped plane, or B of them"""
+        if weight is None:
+            return None, 0
+        planes = unwrap_stack_weight_planes(np.shape(weight), B, self.shape)
+        return np.ascontiguousarray(weight, dtype=self.rdtype), planes
+
+    def _stack_out(self, out, B):
+        phi = out if out is not None else np.empty((B,) + tuple(self.shape), self.rdtype)
+        if phi.shape != (B,) + tuple(self.shape) or phi.dtype != self.rdtype or not phi.flags.c_contiguous:
+            raise ValueError('out must be a C-contiguous (B, n0, n1) array of the plan dtype')
+        return phi
+
+    def _unwrap_stack_run(self, planes, weight, kmax, eps, axes_compat, out):
+        """planes: (psis,) or (dxs, dys), checked and converted.  The stack in calls of at most UNWRAP_BATCH_MAX problems;
+        shapes without a batched unwrap (asked once: gpa_supports_batch) loop over the single call."""
+        B = planes[0].shape[0]
+        w, _ = self._stack_weight(weight, B)
+        phi = self._stack_out(out, B)
+        iters = np.zeros(B, dtype=np.int64)
+        prediff = len(planes) == 2
+        if not self.lib.gpa_supports_batch(self.handle):
+            single = self.unwrap_prediff if prediff else self.unwrap
+            for b in range(B):
+                wb = None if w is None else (w if w.ndim == 2 else w[b])
+                phi[b], iters[b] = single(*[a[b] for a in planes], wb, kmax=kmax, eps=eps, axes_compat=axes_compat)
+            return phi, iters
+        fn = self.lib.gpa_unwrap_prediff_batch if prediff else self.lib.gpa_unwrap_batch
+        for c0 in range(0, B, UNWRAP_BATCH_MAX):
+            n = min(UNWRAP_BATCH_MAX, B - c0)
+            it = (C.c_int * n)()
+            own = w is not None and w.ndim == 3     # (B, n0, n1): one plane per map
+            wc = None if w is None else (w[c0:c0 + n] if own else w)
+            wp = 0 if w is None else (n if own else 1)
+            check(fn(self.handle, *[_ptr(a[c0:c0 + n]) for a in planes], n, _ptr(wc), wp, int(kmax), float(eps),
+                     1 if axes_compat else 0, _ptr(phi[c0:c0 + n]), it),
+                  'gpa_unwrap_prediff_batch' if prediff else 'gpa_unwrap_batch')
+            iters[c0:c0 + n] = it[:]
+        return phi, iters
+
+    def unwrap_stack(self, psis, weight=None, kmax=100, eps=1e-9, axes_compat=True, out=None):
+        """B wrapped phase maps (B, n0, n1) in one device call: (phi (B, n0, n1), iters (B,)).  weight: None, one
+        (n0, n1) plane for all maps or (B, n0, n1), one each.  Map b's phi and count are those of unwrap() on it."""
+        B = unwrap_stack_shapes(np.shape(psis), None, self.shape)
+        psis = np.ascontiguousarray(psis, dtype=self.rdtype)
+        return self._unwrap_stack_run((psis,), weight, kmax, eps, axes_compat, out)
+
+    def unwrap_prediff_stack(self, dxs, dys, weight=None, kmax=100, eps=1e-9, axes_compat=True, out=None):
+        """the same from pre-differenced gradients: dxs (B, n0, n1 - 1), dys (B, n0 - 1, n1)"""
+        B = unwrap_stack_shapes(np.shape(dxs), np.shape(dys), self.shape)
+        dxs = np.ascontiguousarray(dxs, dtype=self.rdtype)
+        dys = np.ascontiguousarray(dys, dtype=self.rdtype)
+        return self._unwrap_stack_run((dxs, dys), weight, kmax, eps, axes_compat, out)
+
+    def unwrap_batch_dev(self, psi_ptr, nb, weight_ptr, weight_planes, phi_ptr, kmax=100, eps=1e-9, axes_compat=True,
+                         want_iters=True):
+        """device pointers (psi nb x n0 x n1, weight weight_planes x n0 x n1 or None with 0, phi nb x n0 x n1 apart from
+        the inputs).  Returns the nb iteration counts, or None without waiting when want_iters is False (pair with
+        unwrap_batch_finish)"""
+        it = (C.c_int * max(1, int(nb)))() if want_iters else None
+        check(self.lib.gpa_unwrap_batch_dev(self.handle, _ptr(psi_ptr), int(nb), _ptr(weight_ptr), int(weight_planes), int(kmax),
+                                            float(eps), 1 if axes_compat else 0, _ptr(phi_ptr), it), 'gpa_unwrap_batch_dev')
+        return None if it is None else np.array(it[:int(nb)], dtype=np.int64)
+
+    def unwrap_prediff_batch_dev(self, dx_ptr, dy_ptr, nb, weight_ptr, weight_planes, phi_ptr, kmax=100, eps=1e-9,
+                                 axes_compat=True, want_iters=True):
+        """unwrap_batch_dev from gradients: dx nb x n0 x (n1 - 1), dy nb x (n0 - 1) x n1"""
+        it = (C.c_int * max(1, int(nb)))() if want_iters else None
+        check(self.lib.gpa_unwrap_prediff_batch_dev(self.handle, _ptr(dx_ptr), _ptr(dy_ptr), int(nb), _ptr(weight_ptr),
+                                                    int(weight_planes), int(kmax), float(eps), 1 if axes_compat else 0,
+                                                    _ptr(phi_ptr), it), 'gpa_unwrap_prediff_batch_dev')
+        return None if it is None else np.array(it[:int(nb)], dtype=np.int64)
+
+    def unwrap_batch_finish(self, nb):
+        """waits for the plan's stream; the nb iteration counts of the last unwrap_*batch_dev call"""
+        it = (C.c_int * max(1, int(nb)))()
+        check(self.lib.gpa_unwrap_batch_finish(self.handle, int(nb), it), 'gpa_unwrap_batch_finish')
+        return np.array(it[:int(nb)], dtype=np.int64)
+
+    def unwrap_batch_problem_bytes(self, kmax=100):
+        """device bytes of one problem of a stack unwrap (UNWRAP_STACK_BYTES divided by this is the chunk of a call)"""
+        return int(self.lib.gpa_unwrap_batch_problem_bytes(self.handle, int(kmax)))
 
     def extract_displacement_field(self, image, kvecs, klists, sigma, mask_border, kmax=10,
                                    want_lockins=False, want_kidx=False, out=None, want_grads=False, want_weights=False,

@@ -254,35 +254,40 @@ int gpa_extract_displacement_field_grad_async(gpa_plan* p, const void* image, co
 }
 
 // ---- batched driver ---------------------------------------------------------------
-// the unwrap workspace of the 2 B problems of B images, their weights and pinned iteration counts.  It is a capacity: fewer
-// frames (a ragged last chunk, a shorter stack) reuse it
+// The plan's batched unwrap workspace, shared by the batched driver (2 problems per image) and the stack unwrap
+// (gpa_unwrap_batch_dev).  It is a capacity in problems: a call that needs fewer (a ragged last chunk, a shorter stack, the
+// other entry point) reuses it, one that needs more rebuilds it.
+int ensure_unwrap_problems(gpa_plan* p, int nprob, const char* who) {
+  if (nprob > p->uwb_probs) {
+    if (!unwrap_supports_batch(&p->uw))   // (asked of the plan's own workspace: nothing is built for a shape that cannot use it)
+      return fail(GPA_ERR_STATE, std::string(who) + ": this image shape has no batched unwrap");
+    HIP_TRY(hipStreamSynchronize(p->stream));
+    if (p->uwb_probs) unwrap_workspace_destroy(&p->uwb);
+    p->uwb_probs = 0;
+    p->uwb_bytes = p->uwb_base_bytes = 0;
+    size_t bb = 0;
+    hipError_t e = unwrap_workspace_create(p->dtype, p->n0, p->n1, p->stream, &p->uwb, &bb, nprob);
+    if (e != hipSuccess) {
+      unwrap_workspace_destroy(&p->uwb);
+      return fail(GPA_ERR_HIP, std::string("batched unwrap workspace: ") + hipGetErrorString(e));
+    }
+    if (!unwrap_supports_batch(&p->uwb)) {
+      unwrap_workspace_destroy(&p->uwb);
+      return fail(GPA_ERR_STATE, std::string(who) + ": this image shape has no batched unwrap");
+    }
+    p->uwb_probs = nprob;
+    p->uwb_bytes = p->uwb_base_bytes = bb;
+  }
+  if (!unwrap_set_active(&p->uwb, nprob)) return fail(GPA_ERR_STATE, "batched unwrap workspace: bad active count");
+  HIP_TRY(p->h_iters_b.reserve((size_t)4 * std::max(nprob, p->uwb_probs) * sizeof(int), p->stream));
+  return GPA_OK;
+}
+
+// the unwrap workspace of the 2 B problems of B images, their weights and pinned iteration counts
 static int ensure_batch_unwrap(gpa_plan* p, int B) {
-  if (B <= p->uwb_images) {
-    if (!unwrap_set_active(&p->uwb, 2 * B)) return fail(GPA_ERR_STATE, "batched unwrap workspace: bad active count");
-    return GPA_OK;
-  }
-  HIP_TRY(hipStreamSynchronize(p->stream));
-  if (p->uwb_images) unwrap_workspace_destroy(&p->uwb);
-  p->uwb_images = 0;
-  p->uwb_bytes = 0;
-  size_t bb = 0;
-  hipError_t e = unwrap_workspace_create(p->dtype, p->n0, p->n1, p->stream, &p->uwb, &bb, 2 * B);
-  if (e != hipSuccess) {
-    unwrap_workspace_destroy(&p->uwb);
-    return fail(GPA_ERR_HIP, std::string("batched unwrap workspace: ") + hipGetErrorString(e));
-  }
-  if (!unwrap_supports_batch(&p->uwb)) {
-    unwrap_workspace_destroy(&p->uwb);
-    return fail(GPA_ERR_STATE, "gpa_extract_displacement_field_batch: this image shape has no batched unwrap");
-  }
-  e = p->d_wnorm_b.reserve((size_t)B * p->n0 * p->n1 * p->rsz, p->stream);
-  if (e == hipSuccess) e = p->h_iters_b.reserve((size_t)8 * B * sizeof(int), p->stream);
-  if (e != hipSuccess) {
-    unwrap_workspace_destroy(&p->uwb);
-    return fail(GPA_ERR_HIP, std::string("batched driver buffers: ") + hipGetErrorString(e));
-  }
-  p->uwb_images = B;
-  p->uwb_bytes = bb;
+  TRY(ensure_unwrap_problems(p, 2 * B, "gpa_extract_displacement_field_batch"));
+  p->uwb_last_nb = 0;   // (gpa_unwrap_batch_finish: the counts in flight are no stack unwrap's)
+  HIP_TRY(p->d_wnorm_b.reserve((size_t)B * p->n0 * p->n1 * p->rsz, p->stream));
   return GPA_OK;
 }
 
@@ -340,6 +345,7 @@ int gpa_extract_displacement_field_batch_dev(gpa_plan* p, const void* images, in
   }
   hipError_t e = unwrap_enqueue_prepared(&p->uwb, p->d_wnorm_b.ptr, nparts, kmax, 1e-9, true, u, p->stream);
   if (e == hipSuccess) e = unwrap_fetch_iters(&p->uwb, p->h_iters_b.as<int>(), p->stream);
+  p->uwb_bytes = p->uwb_base_bytes + unwrap_ring_bytes(&p->uwb);   // (the solve allocates the search directions it keeps)
   if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("batched unwrap: ") + hipGetErrorString(e));
   return iters_out ? read_batch_iters(p, B, iters_out) : GPA_OK;
 }
@@ -352,7 +358,7 @@ int gpa_supports_batch(gpa_plan* p) {
 }
 
 int gpa_last_batch_iters(gpa_plan* p, int B, int* iters_out) {
-  if (!p || !iters_out || B < 1 || B > p->uwb_images) return fail(GPA_ERR_ARG, "gpa_last_batch_iters: bad argument");
+  if (!p || !iters_out || B < 1 || 2 * B > p->uwb_probs) return fail(GPA_ERR_ARG, "gpa_last_batch_iters: bad argument");
   return read_batch_iters(p, B, iters_out);
 }
 

@@ -200,10 +200,15 @@ struct gpa_plan {
   void* d_u = nullptr;            // 2 x n0 x n1
   double* d_kmat = nullptr;       // [max_peaks][2]
   UnwrapWorkspace uw{};
-  // batched driver (gpa_extract_displacement_field_batch_dev): one workspace for the 2 x images solves of a call
+  // ONE batched workspace per plan, its capacity counted in problems: the 2 x images solves of a batched driver call
+  // (gpa_extract_displacement_field_batch_dev) and the problems of a stack unwrap (gpa_unwrap_batch_dev) share it.  Grown to
+  // the largest need seen (ensure_unwrap_problems); smaller calls reuse it through unwrap_set_active.
   UnwrapWorkspace uwb{};
-  int uwb_images = 0;
-  size_t uwb_bytes = 0;           // its device bytes: the one workspace that is rebuilt, so counted beside ws_bytes
+  int uwb_probs = 0;
+  size_t uwb_base_bytes = 0;      // device bytes it was created with
+  size_t uwb_bytes = 0;           // ... and with the search directions allocated since: the one workspace that is rebuilt, so
+                                  // counted beside ws_bytes
+  int uwb_last_nb = 0;            // problems of the last gpa_unwrap_batch[_dev] call (gpa_unwrap_batch_finish)
   DevBuf d_wnorm_b{&ws_bytes};    // images x n0 x n1
   DevBuf h_iters_b{nullptr, true};   // pinned: 4 ints per problem
   // sweep of a chunk of images in one set of launches: x-planes, lock-ins, means, mean scratch (doubles) per image
@@ -295,6 +300,9 @@ int ensure_sf(gpa_plan* p, size_t bytes);
 // at least `bytes` in a buffer of the plan (DevBuf::reserve on the plan's stream), failing in the words of `what`
 int plan_reserve(gpa_plan* p, DevBuf& b, size_t bytes, const char* what);
 int stage_kmat(gpa_plan* p, const double* kvecs, int P);
+// the plan's batched unwrap workspace with room for `nprob` problems, the first nprob of them active, and pinned room for their
+// flag words (gpa_api_driver.hip); GPA_ERR_STATE in the words of `who` where the shape has no batched unwrap
+int ensure_unwrap_problems(gpa_plan* p, int nprob, const char* who);
 // the x-planes pass B reads: those of one image in the plan's own buffer ({p->Tbuf, 1, 0}), or those of a stack of nimg images
 // `stride` planes apart (stride != 0 marks a stack)
 struct XPlanes { const void* T; int nimg, stride; };

@@ -11,8 +11,9 @@ struct UnwrapWorkspace {
 };
 
 // nprob > 1: a workspace for nprob independent solves on images of one shape that run as ONE set of launches
-// (blockIdx.z = problem; prepared starts only).  Problem pb uses the pb-th slice of every buffer; problems 2i and
-// 2i + 1 share the weight of image i (the two displacement components of a batched driver call).
+// (blockIdx.z = problem).  Problem pb uses the pb-th slice of every buffer; in the drivers' solves problems 2i and
+// 2i + 1 share the weight of image i (the two displacement components of a batched driver call), in a stack unwrap
+// (unwrap_enqueue_stack) every problem has its own weight or all share one.
 hipError_t unwrap_workspace_create(int dtype, int n0, int n1, hipStream_t s, UnwrapWorkspace* ws,
                                    size_t* bytes_out, int nprob = 1);
 void unwrap_workspace_destroy(UnwrapWorkspace* ws);
@@ -33,6 +34,20 @@ hipError_t unwrap_run(UnwrapWorkspace* ws, const void* a, const void* b, const v
 // enqueue everything without synchronising, then fetch the iteration count (synchronises s)
 hipError_t unwrap_enqueue(UnwrapWorkspace* ws, const void* a, const void* b, const void* weight, bool from_psi,
                           int kmax, double eps, bool axes_compat, void* phi, hipStream_t s);
+// A stack: the workspace's active problems (unwrap_set_active) solve plane pb of a (psi, or dx) and b (dy) into plane pb
+// of phi, as ONE set of launches on the fused path (hipErrorNotSupported where unwrap_supports_batch says no).  weight:
+// null, one plane per problem (own_weights) or one plane for all.  nb_call: the problems of the whole call where it runs
+// in chunks -- every chunk takes the kernels a launch of nb_call problems takes, so chunking never changes a bit.
+// Problem pb's bits are those of unwrap_enqueue on its planes under the same kernels.
+hipError_t unwrap_enqueue_stack(UnwrapWorkspace* ws, const void* a, const void* b, const void* weight, bool own_weights,
+                                bool from_psi, int nb_call, int kmax, double eps, bool axes_compat, void* phi,
+                                hipStream_t s);
+// the 4 flag words of every active problem into (pinned) host memory, no synchronisation: the count of problem j at
+// host_pinned[4 * j + unwrap_iters_slot()], also for one problem
+hipError_t unwrap_fetch_flags(UnwrapWorkspace* ws, int* host_pinned, hipStream_t s);
+int unwrap_capacity(const UnwrapWorkspace* ws);                  // problems the buffers hold
+size_t unwrap_problem_fixed_bytes(const UnwrapWorkspace* ws);    // per problem, beside its image-sized arrays (gpa_unwrap_batch.h)
+size_t unwrap_ring_bytes(const UnwrapWorkspace* ws);             // search directions allocated since the workspace was created
 // prepared start: the caller has written r0 = div(W^2 wrap(grad)) into unwrap_residual_buffer() and
 // nparts partial sums of ||r0||^2 into unwrap_partials_buffer() (reconstruct_setup_kernel does, fused with
 // the per-pixel least squares that produces the gradients); weight as in unwrap_enqueue

@@ -28,6 +28,14 @@ static __global__ void set_stall_limit_kernel(double* scal, int nprob, double li
   for (int pb = threadIdx.x; pb < nprob; pb += blockDim.x) scal[(size_t)pb * SCAL_N + SC_STALL_LIMIT] = limit;
 }
 
+// the weight map of every solve but the stack unwrap's: problems 2i and 2i + 1 read the weight of image i (the paired and
+// the batched driver; one problem reads plane 0 whatever the map), and the route follows the launch's own problem count
+static void driver_weight_map(Impl* w) {
+  w->wshift = 1;
+  w->wstride = (size_t)w->n0 * w->n1;
+  w->route_nprob = 0;
+}
+
 hipError_t run_pcg(Impl* w, const void* a, const void* b, const void* weight, bool from_psi, int kmax, double eps,
                           int compat, void* phi, hipStream_t s) {
   const int n0 = w->n0, n1 = w->n1;
@@ -42,7 +50,7 @@ hipError_t run_pcg(Impl* w, const void* a, const void* b, const void* weight, bo
     // (gpa_unwrap_route.h has the rules)
     RouteIn in;
     in.dtype = w->dtype; in.n0 = n0; in.n1 = n1; in.lg0 = w->lg0; in.lg1 = w->lg1;
-    in.nprob = w->nprob; in.generic = w->generic; in.mr_ok = w->mr_ok;
+    in.nprob = w->route_nprob > 0 ? w->route_nprob : w->nprob; in.generic = w->generic; in.mr_ok = w->mr_ok;
     in.has_rowhalf = w->tw1h != nullptr;
     in.has_colhalf = w->wk0h != nullptr;
     in.has_tri = w->tritab != nullptr; in.triR = w->triR;
@@ -82,6 +90,7 @@ hipError_t run_pcg(Impl* w, const void* a, const void* b, const void* weight, bo
   }
   hipError_t e;
   const bool fused_path = !w->generic || w->mr_ok;   // the fused 4-kernel iteration
+  if (w->nprob > 1 && !fused_path) return hipErrorNotSupported;   // several problems per launch: the fused path only
   if (a) {
     if ((e = launch_unwrap_setup(w, a, b, weight, from_psi, phi, s)) != hipSuccess) return e;
   } else {
@@ -93,7 +102,6 @@ hipError_t run_pcg(Impl* w, const void* a, const void* b, const void* weight, bo
     if (!fused_path && (e = launch_scal_init(w, w->prepared_parts, s)) != hipSuccess) return e;
   }
   w->iters_slot = fused_path ? 3 : 0;
-  if (w->nprob > 1 && (a || !fused_path)) return hipErrorNotSupported;   // batched: prepared start on the fused path only
   if (fused_path) {
     // 4 kernels per iteration, no scalar kernels.  The phi / r update of iteration it-1 rides in the row-DCT
     // kernel of iteration it; the stopping test is evaluated by the column kernel from that kernel's partial norms.
@@ -102,8 +110,7 @@ hipError_t run_pcg(Impl* w, const void* a, const void* b, const void* weight, bo
     double* part_norm = w->part + 2 * MAXPART;
     // the search directions of the last `ring` iterations stay in HBM (64 MiB each at 4096^2 f32 -- HBM is
     // plentiful), so phi += alpha p costs one pass over phi per `ring` iterations instead of one per iteration
-    int ring = kmax < RING_MAX ? kmax : RING_MAX;
-    if (ring < 2) ring = 2;
+    int ring = unwrap_ring_for(kmax);
     while (w->nring < ring) {
       void* buf = nullptr;
       if (hipMalloc(&buf, npx * w->rsz * w->cap) != hipSuccess) { (void)hipGetLastError(); break; }
@@ -168,7 +175,22 @@ hipError_t unwrap_enqueue(UnwrapWorkspace* ws, const void* a, const void* b, con
                           int kmax, double eps, bool axes_compat, void* phi, hipStream_t s) {
   Impl* w = (Impl*)ws->impl;
   if (!w || !w->supported) return hipErrorNotSupported;
+  driver_weight_map(w);
   return run_pcg(w, a, b, weight, from_psi, kmax, eps, axes_compat ? 1 : 0, phi, s);
+}
+
+hipError_t unwrap_enqueue_stack(UnwrapWorkspace* ws, const void* a, const void* b, const void* weight, bool own_weights,
+                                bool from_psi, int nb_call, int kmax, double eps, bool axes_compat, void* phi,
+                                hipStream_t s) {
+  Impl* w = (Impl*)ws->impl;
+  if (!w || !w->supported) return hipErrorNotSupported;
+  if (!a) return hipErrorInvalidValue;
+  w->wshift = 0;
+  w->wstride = own_weights ? (size_t)w->n0 * w->n1 : 0;
+  w->route_nprob = nb_call;
+  const hipError_t e = run_pcg(w, a, b, weight, from_psi, kmax, eps, axes_compat ? 1 : 0, phi, s);
+  driver_weight_map(w);
+  return e;
 }
 
 void* unwrap_residual_buffer(UnwrapWorkspace* ws, int problem) {
@@ -186,6 +208,7 @@ hipError_t unwrap_enqueue_prepared(UnwrapWorkspace* ws, const void* weight, int 
   if (!w || !w->supported) return hipErrorNotSupported;
   if (nparts < 1 || nparts > MAXPART) return hipErrorInvalidValue;
   w->prepared_parts = nparts;
+  driver_weight_map(w);
   return run_pcg(w, nullptr, nullptr, weight, false, kmax, eps, axes_compat ? 1 : 0, phi, s);
 }
 
@@ -209,6 +232,26 @@ hipError_t unwrap_fetch_iters(UnwrapWorkspace* ws, int* host_pinned, hipStream_t
   // host_pinned[FLAGS_N * j + unwrap_iters_slot()]
   if (w->nprob == 1) return hipMemcpyAsync(host_pinned, w->flags + w->iters_slot, sizeof(int), hipMemcpyDeviceToHost, s);
   return hipMemcpyAsync(host_pinned, w->flags, (size_t)FLAGS_N * w->nprob * sizeof(int), hipMemcpyDeviceToHost, s);
+}
+hipError_t unwrap_fetch_flags(UnwrapWorkspace* ws, int* host_pinned, hipStream_t s) {
+  Impl* w = (Impl*)ws->impl;
+  if (!w || !w->supported) return hipErrorNotSupported;
+  return hipMemcpyAsync(host_pinned, w->flags, (size_t)FLAGS_N * w->nprob * sizeof(int), hipMemcpyDeviceToHost, s);
+}
+int unwrap_capacity(const UnwrapWorkspace* ws) {
+  const Impl* w = (const Impl*)ws->impl;
+  return w ? w->cap : 0;
+}
+size_t unwrap_problem_fixed_bytes(const UnwrapWorkspace* ws) {
+  const Impl* w = (const Impl*)ws->impl;
+  if (!w) return 0;
+  size_t b = (size_t)SCAL_N * sizeof(double) + (size_t)FLAGS_N * sizeof(int) + PART_N * sizeof(double);
+  if (w->strtab) b += (size_t)2 * w->strS * w->n1 * 2 * sizeof(double);   // stragg + strcar: [S][n1] double2 each
+  return b;
+}
+size_t unwrap_ring_bytes(const UnwrapWorkspace* ws) {
+  const Impl* w = (const Impl*)ws->impl;
+  return w && w->nring > 2 ? (size_t)(w->nring - 2) * w->n0 * w->n1 * w->rsz * w->cap : 0;
 }
 // a workspace created for `cap` problems solves the first n of them (n <= cap): a stack whose last chunk is ragged,
 // or a shorter stack, reuses the buffers instead of paying a destroy / create (hipMalloc, table upload) per change

@@ -24,16 +24,20 @@
 #include "gpa_internal.h"
 #include "gpa_unwrap.h"
 #include "gpa_unwrap_route.h"
+#include "gpa_unwrap_batch.h"
 
 namespace gpa {
 
 constexpr int MAXPART = 65536;   // one partial sum per image row / per grid-stride block
 constexpr int RING_MAX = 10;     // search directions kept so that phi is updated once per RING_MAX iterations
+static_assert(RING_MAX == UNWRAP_RING_MAX, "gpa_unwrap_batch.h sizes a stack's chunks with this ring");
 constexpr int SC_ALPHA = 16;     // scal[SC_ALPHA + j % ring] = alpha of iteration j
 // Batched solves: blockIdx.z = problem.  The image-sized arrays of problem pb sit pb * pimg elements behind those of
-// problem 0, its scalars / flags / partial sums SCAL_N / FLAGS_N / PART_N entries behind; problems 2i and 2i + 1 (the
-// two displacement components of image i) share the weight of image i.  A launch with gridDim.z = 1 is the single
-// solve it always was.
+// problem 0, its scalars / flags / partial sums SCAL_N / FLAGS_N / PART_N entries behind; its weight plane sits
+// unwrap_weight_offset(pb, wshift, wstride) behind the first (gpa_unwrap_batch.h: problems 2i and 2i + 1 of the batched
+// driver share the weight of image i, the problems of a stack unwrap have one each or one for all).  The two values are
+// kernel arguments: uniform over a launch, they and the address they give stay in scalar registers, so no instantiation's
+// vector registers change.  A launch with gridDim.z = 1 is the single solve it always was.
 constexpr int SCAL_N = SC_ALPHA + RING_MAX + 6;
 constexpr int FLAGS_N = 4;
 constexpr size_t PART_N = (size_t)3 * MAXPART;
@@ -42,6 +46,9 @@ struct Impl {
   int dtype, n0, n1, lg0, lg1;
   int nprob;                 // problems solved per launch (blockIdx.z): 1, or 2 x images of a batched driver call
   int cap;                   // problems the buffers hold (nprob <= cap: unwrap_set_active)
+  int route_nprob;           // problems of the whole call where it runs in chunks (0: nprob): every chunk takes the call's kernels
+  int wshift;                // weight plane of problem pb: unwrap_weight_offset(pb, wshift, wstride), set per solve by the
+  size_t wstride;            // unwrap_enqueue* entry (gpa_unwrap_batch.h)
   int iters_slot;            // flags[iters_slot] = iterations performed (3: fused iteration, 0: plain scheme)
   Route route;               // the kernels of the current solve (unwrap_route(), once per solve)
   bool supported;

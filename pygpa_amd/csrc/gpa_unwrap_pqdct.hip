@@ -53,12 +53,12 @@ template <class T> __device__ __forceinline__ T wmin(T a, T b) { return a < b ? 
 template <class T, int LG>
 __global__ __launch_bounds__((RowGeom<T, LG>::THREADS), (sizeof(T) == 8 ? GPA_F64_WAVES : GPA_PQDCT_WAVES)) void pqdct_kernel(
     const T* __restrict__ p, const T* __restrict__ wgt, T* __restrict__ Dout, int n0, const cpx<T>* __restrict__ twtab,
-    const cpx<T>* __restrict__ wk, const int* flags, double* part_pq, size_t pimg) {
+    const cpx<T>* __restrict__ wk, const int* flags, double* part_pq, size_t pimg, int wshift, size_t wstride) {
   {
     const size_t pb = blockIdx.z;
     p += pb * pimg;
     Dout += pb * pimg;
-    if (wgt) wgt += (pb >> 1) * pimg;   // the two components of an image share its weight
+    if (wgt) wgt += unwrap_weight_offset(pb, wshift, wstride);
     flags += pb * FLAGS_N;
     part_pq += pb * PART_N;
   }
@@ -222,7 +222,8 @@ hipError_t run_pqdct(const Impl* w, const void* p, const void* weight, double* p
   *npq = grid;
   GPA_PROF("pqdct_kernel", s);
   kern<<<dim3(grid, 1, w->nprob), G::THREADS, G::LDS_BYTES, s>>>((const T*)p, (const T*)weight, (T*)w->q, w->n0, (const cpx<T>*)w->tw1,
-                                                               (const cpx<T>*)w->wk1, w->flags, part_pq, (size_t)w->n0 * w->n1);
+                                                               (const cpx<T>*)w->wk1, w->flags, part_pq, (size_t)w->n0 * w->n1,
+                                                               w->wshift, w->wstride);
   return hipGetLastError();
 }
 }  // namespace

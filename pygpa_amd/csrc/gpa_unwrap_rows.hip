@@ -275,14 +275,14 @@ template <class T, int LG>
 __global__ __launch_bounds__((RowPqGeom<T, LG>::THREADS)) void rowidct_pq_kernel(
     const T* __restrict__ Z, const T* __restrict__ pin, T* __restrict__ pout, const T* __restrict__ wgt,
     T* __restrict__ q, int n0, const cpx<T>* __restrict__ twtab, const cpx<T>* __restrict__ wk, const int* flags,
-    const double* part_rho, int nrho, double* part_pq, double* scal, int it, size_t pimg) {
+    const double* part_rho, int nrho, double* part_pq, double* scal, int it, size_t pimg, int wshift, size_t wstride) {
   {
     const size_t pb = blockIdx.z;
     Z += pb * pimg;
     pin += pb * pimg;
     pout += pb * pimg;
     q += pb * pimg;
-    if (wgt) wgt += (pb >> 1) * pimg;   // the two components of an image share its weight
+    if (wgt) wgt += unwrap_weight_offset(pb, wshift, wstride);
     flags += pb * FLAGS_N;
     scal += pb * SCAL_N;
     part_rho += pb * PART_N;
@@ -495,7 +495,8 @@ hipError_t run_rowidct_pq(const Impl* w, const void* pin, void* pout, const void
     GPA_PROF("rowidct_pq_kernel", s);
     kern<<<dim3(grid, 1, w->nprob), H::THREADS, H::LDS_BYTES, s>>>((const T*)w->z, (const T*)pin, (T*)pout, (const T*)weight,
                                                  (T*)w->q, w->n0, (const cpx<T>*)w->tw1, (const cpx<T>*)w->wk1, w->flags,
-                                                 part_rho, nrho, part_pq, w->scal, it, (size_t)w->n0 * w->n1);
+                                                 part_rho, nrho, part_pq, w->scal, it, (size_t)w->n0 * w->n1, w->wshift,
+                                                 w->wstride);
     return hipGetLastError();
   }
 }

@@ -43,7 +43,19 @@ constexpr int SETUP_ROWS = 16;   // rows per workgroup band of setup_kernel
 template <class T>
 __global__ __launch_bounds__(256) void setup_kernel(const T* __restrict__ a, const T* __restrict__ b,
                                                    const T* __restrict__ w, int from_psi, int n0, int n1,
-                                                   T* __restrict__ r, T* __restrict__ phi, double* part) {
+                                                   T* __restrict__ r, T* __restrict__ phi, double* part,
+                                                   size_t astride, size_t bstride, int wshift, size_t wstride) {
+  {
+    // blockIdx.z = problem of a stack: its planes of a (psi: n0 x n1, dx: n0 x (n1 - 1)) and b (dy: (n0 - 1) x n1), its
+    // weight plane, its slice of r, its own phi and its partial sums.  Everything below is the single problem's arithmetic.
+    const size_t pb = blockIdx.z, pimg = (size_t)n0 * n1;
+    a += pb * astride;
+    if (b) b += pb * bstride;
+    if (w) w += unwrap_weight_offset(pb, wshift, wstride);
+    r += pb * pimg;
+    phi += pb * pimg;
+    part += pb * PART_N;
+  }
   __shared__ double sh[256];
   const int y = blockIdx.x * 256 + threadIdx.x;
   const int x0 = blockIdx.y * SETUP_ROWS;
@@ -210,13 +222,13 @@ __global__ __launch_bounds__(256) void pq_kernel(const T* __restrict__ z, const 
                                                 T* __restrict__ pout, const T* __restrict__ w, int n0, int n1,
                                                 T* __restrict__ q, double* part, double* scal,
                                                 const int* flags, const double* part_rho, int nrho, int it,
-                                                int band, size_t pimg = 0) {
+                                                int band, size_t pimg = 0, int wshift = 0, size_t wstride = 0) {
   {
     const size_t pb = blockIdx.z;
     z += pb * pimg;
     if (pin) pin += pb * pimg;
     if (pout) pout += pb * pimg;
-    if (w) w += (pb >> 1) * pimg;   // the two components of an image share its weight
+    if (w) w += unwrap_weight_offset(pb, wshift, wstride);
     if (q) q += pb * pimg;          // (q == nullptr: the last iteration of a solve needs <p, q> only)
     part += pb * PART_N;
     scal += pb * SCAL_N;
@@ -325,11 +337,12 @@ __global__ __launch_bounds__(256) void pq_kernel(const T* __restrict__ z, const 
 // same order as pq_kernel<T, true, V>: results and partial sums are bit-identical.
 template <class T, int V, int BAND>
 __global__ __launch_bounds__(256) void pq_small_kernel(const T* __restrict__ p, const T* __restrict__ w, int n0, int n1,
-                                                      T* __restrict__ q, double* part, const int* flags, size_t pimg) {
+                                                      T* __restrict__ q, double* part, const int* flags, size_t pimg,
+                                                      int wshift, size_t wstride) {
   {
     const size_t pb = blockIdx.z;
     p += pb * pimg;
-    if (w) w += (pb >> 1) * pimg;   // the two components of an image share its weight
+    if (w) w += unwrap_weight_offset(pb, wshift, wstride);
     q += pb * pimg;
     part += pb * PART_N;
     flags += pb * FLAGS_N;
@@ -504,9 +517,13 @@ hipError_t setup_t(const Impl* w, const void* a, const void* b, const void* weig
   const dim3 gsu((w->n1 + 255) / 256, (w->n0 + SETUP_ROWS - 1) / SETUP_ROWS);
   const int nsu = gsu.x * gsu.y;
   if (nsu > MAXPART) return hipErrorInvalidValue;
-  setup_kernel<T><<<gsu, 256, 0, s>>>((const T*)a, (const T*)b, (const T*)weight, from_psi ? 1 : 0, w->n0, w->n1, (T*)w->r,
-                                      (T*)phi, w->part);
-  scal_init_kernel<<<1, 256, 0, s>>>(w->part, nsu, w->scal, w->flags);
+  // a stack (w->nprob problems): plane pb of psi, or of dx and dy, to the pb-th slice of r, phi plane and partial sums
+  const size_t n0 = w->n0, n1 = w->n1;
+  const size_t astride = from_psi ? n0 * n1 : n0 * (n1 - 1), bstride = (n0 - 1) * n1;
+  setup_kernel<T><<<dim3(gsu.x, gsu.y, w->nprob), 256, 0, s>>>((const T*)a, (const T*)b, (const T*)weight, from_psi ? 1 : 0, w->n0,
+                                                             w->n1, (T*)w->r, (T*)phi, w->part, astride, bstride, w->wshift,
+                                                             w->wstride);
+  scal_init_kernel<<<dim3(1, 1, w->nprob), 256, 0, s>>>(w->part, nsu, w->scal, w->flags);
   return hipGetLastError();
 }
 
@@ -518,14 +535,16 @@ hipError_t pq_t(const Impl* w, const void* p, const void* weight, int it, double
   const dim3 grid(g.g.x, g.g.y, w->nprob);
   GPA_PROF("pq_kernel", s);
   if (g.band == 4 && w->route.lat_pq && npx <= ((size_t)1 << 20)) {
-    if (g.V == 4) pq_small_kernel<T, 4, 4><<<grid, 256, 0, s>>>((const T*)p, (const T*)weight, n0, n1, (T*)w->q, part_pq, w->flags, npx);
-    else pq_small_kernel<T, 1, 4><<<grid, 256, 0, s>>>((const T*)p, (const T*)weight, n0, n1, (T*)w->q, part_pq, w->flags, npx);
+    if (g.V == 4) pq_small_kernel<T, 4, 4><<<grid, 256, 0, s>>>((const T*)p, (const T*)weight, n0, n1, (T*)w->q, part_pq, w->flags, npx,
+                                                                w->wshift, w->wstride);
+    else pq_small_kernel<T, 1, 4><<<grid, 256, 0, s>>>((const T*)p, (const T*)weight, n0, n1, (T*)w->q, part_pq, w->flags, npx,
+                                                       w->wshift, w->wstride);
   } else if (g.V == 4) {
     pq_kernel<T, true, 4><<<grid, 256, 0, s>>>((const T*)p, nullptr, nullptr, (const T*)weight, n0, n1, need_q ? (T*)w->q : nullptr,
-                                               part_pq, w->scal, w->flags, nullptr, 0, it, g.band, npx);
+                                               part_pq, w->scal, w->flags, nullptr, 0, it, g.band, npx, w->wshift, w->wstride);
   } else {
     pq_kernel<T, true, 1><<<grid, 256, 0, s>>>((const T*)p, nullptr, nullptr, (const T*)weight, n0, n1, need_q ? (T*)w->q : nullptr,
-                                               part_pq, w->scal, w->flags, nullptr, 0, it, g.band, npx);
+                                               part_pq, w->scal, w->flags, nullptr, 0, it, g.band, npx, w->wshift, w->wstride);
   }
   return hipGetLastError();
 }

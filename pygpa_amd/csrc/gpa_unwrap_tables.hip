@@ -112,6 +112,9 @@ hipError_t unwrap_workspace_create(int dtype, int n0, int n1, hipStream_t s, Unw
   const size_t npx = (size_t)n0 * n1;
   hipError_t e;
   void** arrs[] = {&w->r, &w->p, &w->p2, &w->q, &w->z};
+  static_assert(sizeof(arrs) / sizeof(arrs[0]) == UNWRAP_WS_PLANES, "gpa_unwrap_batch.h counts these planes");
+  w->wshift = 1;   // (the drivers' weight map; every unwrap_enqueue* entry sets its own)
+  w->wstride = npx;
   for (void** a : arrs) {
     e = hipMalloc(a, npx * w->rsz * w->cap);
     if (e != hipSuccess) return e;
@@ -126,6 +129,8 @@ hipError_t unwrap_workspace_create(int dtype, int n0, int n1, hipStream_t s, Unw
   if (e != hipSuccess) return e;
   e = hipMalloc((void**)&w->part, PART_N * w->cap * sizeof(double));
   if (e != hipSuccess) return e;
+  // (1.5 MiB of partial sums per problem: more than the image-sized arrays of a 64 x 64 problem)
+  bytes += ((size_t)SCAL_N * sizeof(double) + (size_t)FLAGS_N * sizeof(int) + PART_N * sizeof(double)) * w->cap;
   if (w->supported && w->generic) {
     for (int ax = 0; ax < 2; ++ax) {
       const int n = ax == 0 ? n0 : n1, lgb = ax == 0 ? w->lgb0 : w->lgb1, L = 1 << lgb, tpf = L / 16;
