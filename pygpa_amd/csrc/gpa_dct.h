@@ -26,6 +26,20 @@ template <class T> GPA_HD T fast_recip(T x) {
   return T(1) / x;
 }
 
+// u = w_k V_k of one real sequence's spectrum V (w_k = (c, -s)): Re u = X_k / 2 and Im u = -X_(N-k) / 2, both by cancellation
+// from terms of size |V|.  The fused solves scale the two parts by 1 / eigenvalue of bins k and N - k -- up to N^2 apart --
+// and the thread of bin N - k forms the same two coefficients from conj(V_k) and w_(N-k) = (s, -c).  Unless both threads
+// round a coefficient identically, the inverse transform of a packed pair turns the difference, times 1 / eigenvalue_k, into bin
+// N - k of the partner sequence (f64, 8192-point columns: 6e4 x the rounding floor).  So: written out with one rounded
+// product and one fma each, the SAME operations on the same numbers in either thread, given tables with w_(N-k) = (s_k, -c_k)
+// to the bit (dct_mirror_exact_w, gpa_unwrap_tables.hip); not left to cmul and the compiler's choice of contraction.
+template <class T> GPA_HD cpx<T> dct_split_mul(cpx<T> w, cpx<T> v) {
+  const T c = w.x, s = -w.y;
+  const T re = fma(c, v.x, s * v.y);        // thread N - k: c' = s, s' = c, v' = conj(v): fma(s, v.x, c * (-v.y)) = mir below
+  const T mir = fma(s, v.x, c * (-v.y));
+  return {re, -mir};
+}
+
 // slot of the permuted sequence -> index in the original sequence
 // (valid for odd N too: the first ceil(N/2) slots take the even samples)
 GPA_HD int makhoul_src(int m, int N) { return m < (N + 1) / 2 ? 2 * m : 2 * (N - 1 - m) + 1; }
@@ -143,7 +157,7 @@ struct WgDCT {
       // split the packed transform: Va = (Zk + conj Zm)/2, Vb = (Zk - conj Zm)/(2i)
       const cpx<T> va = {T(0.5) * (zk.x + zm.x), T(0.5) * (zk.y - zm.y)};
       const cpx<T> vb = {T(0.5) * (zk.y + zm.y), T(-0.5) * (zk.x - zm.x)};
-      const cpx<T> ua = cmul(w, va), ub = cmul(w, vb);
+      const cpx<T> ua = dct_split_mul(w, va), ub = dct_split_mul(w, vb);
       const T cn = T(-0.5) * inv_n;   // 1 / (2 (cos + cos - 2)) / N = cn / (ha + hb)
       T sa = cn * fast_recip(h + hb_a), sb = cn * fast_recip(h + hb_b);
       T sam = cn * fast_recip(hm + hb_a), sbm = cn * fast_recip(hm + hb_b);

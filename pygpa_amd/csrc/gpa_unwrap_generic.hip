@@ -171,7 +171,7 @@ __global__ __launch_bounds__((GenGeom<T, LG>::THREADS)) void g_colsolve_kernel(
       const T h = ha[k], hm = ham[k];
       const cpx<T> qa = {T(0.5) * (zk.x + zm.x), T(0.5) * (zk.y - zm.y)};
       const cpx<T> qb = {T(0.5) * (zk.y + zm.y), T(-0.5) * (zk.x - zm.x)};
-      const cpx<T> ua = cmul(w, qa), ub = cmul(w, qb);
+      const cpx<T> ua = dct_split_mul(w, qa), ub = dct_split_mul(w, qb);   // (one rounding per coefficient in both threads that form it: gpa_dct.h)
       T sa = inv_n / (T(-2) * (h + hba)), sb = inv_n / (T(-2) * (h + hbb));
       T sam = inv_n / (T(-2) * (hm + hba)), sbm = inv_n / (T(-2) * (hm + hbb));
       if (k == 0) {

@@ -347,7 +347,7 @@ __global__ __launch_bounds__(MAXT) void mr_colsolve_kernel(
       const T h = ha[k], hm = ham[k];
       const cpx<T> qa = {T(0.5) * (zk[i].x + zm[i].x), T(0.5) * (zk[i].y - zm[i].y)};
       const cpx<T> qb = {T(0.5) * (zk[i].y + zm[i].y), T(-0.5) * (zk[i].x - zm[i].x)};
-      const cpx<T> ua = cmul(w, qa), ub = cmul(w, qb);
+      const cpx<T> ua = dct_split_mul(w, qa), ub = dct_split_mul(w, qb);   // (one rounding per coefficient in both threads that form it: gpa_dct.h)
       T sa = cn * fast_recip(h + hba), sb = cn * fast_recip(h + hbb);
       T sam = cn * fast_recip(hm + hba), sbm = cn * fast_recip(hm + hbb);
       if (k == 0) {

@@ -29,6 +29,11 @@ namespace gpa {
 #define GPA_ROWPQ_MAXLG 9   // rows up to 512 pixels: row kernel and stencil in one launch (rowidct_pq_kernel)
 #endif
 
+// ---- which shapes the power-of-two kernels take (gpa_unwrap_tables.hip: Impl::generic is the negation) ----
+// both axes powers of two of 64 .. 16384 points (lg = -1: no power of two).  Anything else -- 32 x 8192 as much as
+// 1000 x 1000 -- is a generic shape: the mixed-radix engine where it has a plan, the plain scheme otherwise.
+constexpr bool unwrap_pow2_shape(int lg0, int lg1) { return lg0 >= 6 && lg1 >= 6 && lg0 <= 14 && lg1 <= 14; }
+
 // ---- which tables a workspace gets (gpa_unwrap_tables.hip builds exactly these) ----
 // power-of-two shapes: twiddles of length n1 / 2 for the half-length row kernels (rows of 4096 points can be switched to
 // them for measurements: ROWHALF_MINLG; f64 takes the forward one there by default)

@@ -42,6 +42,17 @@ hipError_t upload(int dtype, void** dst, const std::vector<double>& v, size_t* b
   return dtype == 0 ? upload_vec<float>(dst, v, bytes, s) : upload_vec<double>(dst, v, bytes, s);
 }
 
+// w_k = exp(-i pi k / 2n) = (c_k, -s_k) of the DCT pre / post-processing, with w_(n-k) = (s_k, -c_k) TO THE BIT: the column
+// solves form every coefficient in the threads of bins k and n - k and need both to round alike (dct_split_mul, gpa_dct.h);
+// cos and sin of the two angles evaluated independently differ in the last bit of a double
+static void dct_mirror_exact_w(int n, int k, double* re, double* im) {
+  const int kk = 2 * k <= n ? k : n - k;
+  const double c = cos(M_PI * kk / (2.0 * n));
+  const double s = 2 * kk == n ? c : sin(M_PI * kk / (2.0 * n));
+  *re = kk == k ? c : s;
+  *im = kk == k ? -s : -c;
+}
+
 int ilog2_exact(int n) {
   int lg = 0;
   while ((1 << lg) < n) ++lg;
@@ -102,7 +113,7 @@ hipError_t unwrap_workspace_create(int dtype, int n0, int n1, hipStream_t s, Unw
   // transform-free solves or the half-length kernel down the columns); the Bluestein / mixed-radix engines of the other
   // sizes need a whole transform in LDS: 16384 points in f32, 8192 in f64
   const int maxlg = dtype == 0 ? 14 : 13;
-  const bool pow2ok = w->lg0 >= 6 && w->lg1 >= 6 && w->lg0 <= 14 && w->lg1 <= 14;
+  const bool pow2ok = unwrap_pow2_shape(w->lg0, w->lg1);
   auto blue_lg = [](int n) { int lg = 6; while ((1 << lg) < 2 * n - 1) ++lg; return lg; };
   w->lgb0 = blue_lg(n0);
   w->lgb1 = blue_lg(n1);
@@ -143,7 +154,7 @@ hipError_t unwrap_workspace_create(int dtype, int n0, int n1, hipStream_t s, Unw
         ch[2 * m] = cr; ch[2 * m + 1] = ci;
         bre[m] = cr; bim[m] = ci;
         if (m > 0) { bre[L - m] = cr; bim[L - m] = ci; }
-        wkv[2 * m] = cos(-M_PI * m / (2.0 * n)); wkv[2 * m + 1] = sin(-M_PI * m / (2.0 * n));
+        dct_mirror_exact_w(n, m, &wkv[2 * m], &wkv[2 * m + 1]);
       }
       host_fft(bre, bim);
       std::vector<double> bs((size_t)2 * L);
@@ -269,8 +280,7 @@ hipError_t unwrap_workspace_create(int dtype, int n0, int n1, hipStream_t s, Unw
       for (int i = 0; i < E0; ++i)
         for (int tt = 0; tt < tpf0; ++tt) {
           const int k = spec_index_rt(w->lg0, tt, i, E0);
-          t[2 * ((size_t)i * tpf0 + tt)] = cos(-M_PI * k / (2.0 * n0));
-          t[2 * ((size_t)i * tpf0 + tt) + 1] = sin(-M_PI * k / (2.0 * n0));
+          dct_mirror_exact_w(n0, k, &t[2 * ((size_t)i * tpf0 + tt)], &t[2 * ((size_t)i * tpf0 + tt) + 1]);
         }
       e = upload(dtype, &w->wk0s, t, &bytes, s);
       if (e != hipSuccess) return e;

@@ -3,6 +3,7 @@
 //       <f32|f64> <n0> <n1> [nprob=<n>] [generic] [NO_LAT] [NO_ROWHALF] [ROWHALF_MINLG=<lg>] [NO_ROWPERS] [NO_ROWPQ]
 //       [NO_PQDCT] [COLSOLVE=<tri|fft|stream>]
 //     -> fwd inv cols rowpq fuse_pq lat_rows lat_cols lat_pq      (inv is "-" where rowpq: the kernel is not launched)
+//     (a shape outside unwrap_pow2_shape() -- 1000 x 1000, but also 32 x 8192 -- is generic with or without the word)
 //   unwrap_route_table coupling   every power-of-two shape 64 .. 16384 per axis, both dtypes, every option combination:
 //     the route never names a family whose table the unwrap_builds_*() functions say is absent, or that has no
 //     instantiation for the shape; prints "OK <calls>".
@@ -27,11 +28,13 @@ static int ilog2_exact(int n) {
   return (1 << lg) == n ? lg : -1;
 }
 
-// shape and default tables; generic sizes are taken with a mixed-radix plan (mr_ok)
+// shape and default tables; generic sizes are taken with a mixed-radix plan (mr_ok).  A shape is generic where the caller says
+// so and wherever the workspace makes it so: unwrap_pow2_shape() -- a power-of-two axis under 64 points has no power-of-two kernels
 static RouteIn workspace(int dtype, int n0, int n1, bool generic) {
   RouteIn in;
   in.dtype = dtype; in.n0 = n0; in.n1 = n1;
   in.lg0 = ilog2_exact(n0); in.lg1 = ilog2_exact(n1);
+  generic = generic || !unwrap_pow2_shape(in.lg0, in.lg1);
   in.generic = generic; in.mr_ok = generic;
   in.has_rowhalf = !generic && unwrap_builds_rowhalf(in.lg1);
   in.has_colhalf = !generic && unwrap_builds_colhalf(dtype, in.lg0);

@@ -52,7 +52,10 @@ def solve_profiled(shape, dtype, dx, dy, w, kmax):
 # multiplies the f32 rounding of a row transform (~1e-7 per pass) by up to N^2 / pi^2 = 2.7e7 at N = 16384; the iteration
 # corrects most of it, what is left is a smooth offset whose size is a matter of the rounding's luck: over 12 problems (seeds) the
 # error at 64 x 16384 is 3e-4 .. 2.7e-3 of max|phi| (median 7e-4), at 128 x 8192 4e-5 .. 3.3e-4 (median 8e-5) -- the same
-# distribution for the one-row-per-workgroup and the persistent row kernels (tools/dbg/halfpers_seeds.py, round 6)
+# distribution for the one-row-per-workgroup and the persistent row kernels (tools/dbg/halfpers_seeds.py, round 6).
+# So these numbers are set by the amplification, not by the kernels, and an accuracy regression common to both kernel families
+# would pass them: long f32 rows are held to a rounding-level bound in tests/test_gpu_unwrap_modes.py, per DCT mode with the
+# amplification undone (64 x 8192 and 64 x 16384, persistent and one-row-per-workgroup: 0.5 .. 1.4 of a plain f32 solve).
 F32_TOL = {8192: 6e-4, 16384: 4e-3}
 
 
