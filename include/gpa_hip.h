@@ -273,6 +273,21 @@ int gpa_extract_displacement_field_batch_dev(gpa_plan* plan, const void* images,
                                              const double* kvecs, int P, const double* klists, int K,
                                              double sigma, int mask_border, int kmax, void* u,
                                              int* iters_out);
+/* The stack call that also hands out what the sweep knows, per frame: the arguments of
+ * gpa_extract_displacement_field_batch_dev (the same B range) and the optional outputs of
+ * gpa_extract_displacement_field_grad_dev with one leading frame axis each -- lockins B x P x n0 x n1 complex, kidx
+ * B x P x n0 x n1 int32, grads B x P x n0 x n1 x 2, absw B x P x n0 x n1 -- each nullable.  Frame b's outputs are those of
+ * gpa_extract_displacement_field_grad_dev on frame b, bit for bit.  With all four NULL the call enqueues exactly what
+ * gpa_extract_displacement_field_batch_dev enqueues.  With grads != NULL a chunk of frames is one set of launches for pass A,
+ * pass B with phases, the stencil, |lock-in| and the unwrap set-up, and the 2 B unwraps stay one chain; the candidate phases
+ * of a chunk (chunk x P K n0 n1 reals of plan scratch, counted in gpa_plan_workspace_bytes) bound the chunk at ~3 GB, as
+ * the x-planes do.  iters_out NULL: no synchronisation, gpa_last_batch_iters reads the counts.  Shapes for which
+ * gpa_supports_batch answers 0 are refused (GPA_ERR_STATE).                                                             */
+int gpa_extract_displacement_field_grad_batch_dev(gpa_plan* plan, const void* images, int B,
+                                                  const double* kvecs, int P, const double* klists, int K,
+                                                  double sigma, int mask_border, int kmax, int grad_mode, void* u,
+                                                  void* lockins, int32_t* kidx, void* grads, void* absw,
+                                                  int* iters_out);
 /* waits for the plan's stream and returns the 2 B iteration counts of the last batch call (B <= its stack size) */
 int gpa_last_batch_iters(gpa_plan* plan, int B, int* iters_out);
 /* 1 if the batch call above covers the plan's image shape (every shape whose unwrap runs the fused
@@ -468,6 +483,21 @@ int gpa_phases_jacobian(int device, int dtype, int n0, int n1, int P, const doub
 int gpa_phases_jacobian_dev(int device, int dtype, int n0, int n1, int P, const double* kvecs, const void* phases,
                             const void* weights, double nmperpixel, int add_identity, void* J, void* props,
                             double refangle, double refscale, int diff, void* stream);
+/* gpa_gradients_jacobian: the third source, the phase gradients and weights a one-sweep driver call hands out
+ * (gpa_extract_displacement_field_grad*), for a stack of frames and without a plan.  grads is nimg x P x n0 x n1 x 2, weights
+ * nimg x P x n0 x n1, 2 <= P <= 8, n0, n1 >= 1 with n0 n1 < 2^31; kvecs P x 2 (host); dks NULL or P x 2 (host) with the iso_ref
+ * meaning of gpa_phasegradient2J: g <- wrapToPi(g - 2 pi dk) against 2 pi (kvecs + dks).  J (nimg x n0 x n1 x 2 x 2) is
+ * gpa_phasegradient2J's of every frame, bit for bit (I + J with add_identity), 0 where every weight of a pixel is 0; props
+ * (nimg x 4 x n0 x n1) is gpa_props_from_jac(add_identity = 1) of the plain J, bit for bit.  Either may be NULL, not both: with
+ * props alone J never goes to memory (3 P reals in and 4 out per pixel, against 3 P + 12 of the two-kernel chain).  A device
+ * J must be aligned to 4 elements, device grads to 2.  Errors as above (an axis < 1 here).                                  */
+int gpa_gradients_jacobian(int device, int dtype, int nimg, int n0, int n1, int P, const double* kvecs,
+                           const double* dks, const void* grads, const void* weights, double nmperpixel,
+                           int add_identity, void* J, void* props, double refangle, double refscale, int diff);
+int gpa_gradients_jacobian_dev(int device, int dtype, int nimg, int n0, int n1, int P, const double* kvecs,
+                               const double* dks, const void* grads, const void* weights, double nmperpixel,
+                               int add_identity, void* J, void* props, double refangle, double refscale, int diff,
+                               void* stream);
 int gpa_phys_props_from_jac(int device, int dtype, size_t npx, const void* jac, int add_identity, double refangle,
                             double refscale, int diff, double poisson_ratio, void* props);
 int gpa_phys_props_from_jac_dev(int device, int dtype, size_t npx, const void* jac, int add_identity,

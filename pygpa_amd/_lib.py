@@ -75,6 +75,8 @@ SIGNATURES = {
     'gpa_extract_displacement_field_grad_dev': (_i, [_vp, _vp, _vp, _i, _vp, _i, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _vp, _vp]),
     'gpa_extract_displacement_field_grad_async': (_i, [_vp, _vp, _vp, _i, _vp, _i, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _vp]),
     'gpa_extract_displacement_field_batch_dev': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _d, _i, _i, _vp, _vp]),
+    'gpa_extract_displacement_field_grad_batch_dev': (_i, [_vp, _vp, _i, _vp, _i, _vp, _i, _d, _i, _i, _i, _vp, _vp, _vp, _vp, _vp,
+                                                           _vp]),
     'gpa_last_batch_iters': (_i, [_vp, _i, _vp]),
     'gpa_supports_batch': (_i, [_vp]),
     'gpa_extract_gradients': (_i, [_vp, _vp, _vp, _i, _vp, _i, _d, _i, _vp, _vp, _vp]),
@@ -101,6 +103,8 @@ SIGNATURES = {
     'gpa_field_jacobian_dev': (_i, [_i, _i, _i, _i, _i, _vp, _d, _i, _vp, _vp, _d, _d, _i, _vp]),
     'gpa_phases_jacobian': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _d, _i, _vp, _vp, _d, _d, _i]),
     'gpa_phases_jacobian_dev': (_i, [_i, _i, _i, _i, _i, _vp, _vp, _vp, _d, _i, _vp, _vp, _d, _d, _i, _vp]),
+    'gpa_gradients_jacobian': (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _d, _i, _vp, _vp, _d, _d, _i]),
+    'gpa_gradients_jacobian_dev': (_i, [_i, _i, _i, _i, _i, _i, _vp, _vp, _vp, _vp, _d, _i, _vp, _vp, _d, _d, _i, _vp]),
     'gpa_phys_props_from_jac': (_i, [_i, _i, _sz, _vp, _i, _d, _d, _i, _d, _vp]),
     'gpa_phys_props_from_jac_dev': (_i, [_i, _i, _sz, _vp, _i, _d, _d, _i, _d, _vp, _vp]),
     'gpa_fit_plane': (_i, [_vp, _vp, _i, _d, _dp, _ip]),
@@ -1296,23 +1300,53 @@ class Plan:
               'gpa_extract_displacement_field_batch_dev')
         return None if it is None else np.array(it[:], dtype=np.int64).reshape(int(nimages), 2)
 
-    def extract_displacement_field_stack(self, images, kvecs, klists, sigma, mask_border, kmax=10, chunk=None, out=None):
+    def extract_displacement_field_grad_batch_dev(self, images_ptr, nimages, kvecs, klists, sigma, mask_border, kmax, u_ptr,
+                                                  lockins_ptr=None, kidx_ptr=None, grads_ptr=None, weights_ptr=None, grad_mode=0,
+                                                  want_iters=True):
+        """extract_displacement_field_batch_dev with the optional outputs of extract_displacement_field_dev, one leading frame
+        axis each (device pointers): lockins nimages x P x n0 x n1 complex, kidx the same in int32, grads nimages x P x n0 x n1 x 2,
+        weights nimages x P x n0 x n1.  With none of them the launches are those of extract_displacement_field_batch_dev."""
+        kvecs, P, klists, K = _peak_lists(kvecs, klists)
+        it = (C.c_int * (2 * int(nimages)))() if want_iters else None
+        check(self.lib.gpa_extract_displacement_field_grad_batch_dev(self.handle, _ptr(images_ptr), int(nimages), _ptr(kvecs), P,
+                                                                     _ptr(klists), K, float(sigma), int(mask_border), int(kmax),
+                                                                     int(grad_mode), _ptr(u_ptr), _ptr(lockins_ptr), _ptr(kidx_ptr),
+                                                                     _ptr(grads_ptr), _ptr(weights_ptr), it),
+              'gpa_extract_displacement_field_grad_batch_dev')
+        return None if it is None else np.array(it[:], dtype=np.int64).reshape(int(nimages), 2)
+
+    def extract_displacement_field_stack(self, images, kvecs, klists, sigma, mask_border, kmax=10, chunk=None, out=None,
+                                         want_lockins=False, want_kidx=False, want_grads=False, want_weights=False, grad_mode=0,
+                                         out_lockins=None, out_kidx=None, out_grads=None, out_weights=None):
         """host arrays: images (B, n0, n1) -> u (B, 2, n0, n1) (written into `out` if given) and the (B, 2)
         iteration counts, through extract_displacement_field_batch_dev.  The stack goes through the GPU in chunks of
         `chunk` frames (default: ~16 Mpixel per chunk) on two sets of device buffers: while the GPU works on chunk i a
         host thread uploads chunk i + 1 and another downloads chunk i - 1 (PCIe is full duplex, plain hipMemcpy on the
-        default stream does not wait for the plan's non-blocking streams, ctypes releases the GIL)."""
+        default stream does not wait for the plan's non-blocking streams, ctypes releases the GIL).
+        want_lockins / want_kidx / want_grads / want_weights (or an out_* buffer to write into): the per-frame outputs of
+        extract_displacement_field with a leading frame axis, from the same sweep (extract_displacement_field_grad_batch_dev);
+        the return value is then (u, iters, lockins, kidx, grads, weights) with None for what was not asked for.  The default
+        chunk shrinks by what a frame adds to u's two reals per pixel, so a chunk's outputs stay near the same budget."""
         from concurrent.futures import ThreadPoolExecutor
         images = np.asarray(images)
         if images.ndim != 3 or images.shape[1:] != tuple(self.shape):
             raise ValueError('images must be (B, %d, %d)' % tuple(self.shape))
         B = images.shape[0]
         npx = int(self.shape[0]) * int(self.shape[1])
+        item = np.dtype(self.rdtype).itemsize
+        P = len(_peak_lists(kvecs, klists)[0])
+        # name -> (asked for, caller's buffer, shape after the frame axis, dtype)
+        extras = {'lockins': (want_lockins, out_lockins, (P,) + tuple(self.shape), self.cdtype),
+                  'kidx': (want_kidx, out_kidx, (P,) + tuple(self.shape), np.int32),
+                  'grads': (want_grads, out_grads, (P,) + tuple(self.shape) + (2,), self.rdtype),
+                  'weights': (want_weights, out_weights, (P,) + tuple(self.shape), self.rdtype)}
+        extras = {k: v for k, v in extras.items() if v[0] or v[1] is not None}
+        if extras:
+            return self._extract_stack_outputs(images, kvecs, klists, sigma, mask_border, kmax, chunk, out, extras, grad_mode)
         if chunk is None:
             chunk = max(1, min(B, (16 << 20) // npx))
         chunk = int(max(1, min(chunk, B, 4096)))     # the batched driver takes at most 4096 frames per call
         nchunks = -(-B // chunk)
-        item = np.dtype(self.rdtype).itemsize
         # (a plain array: page-locking hundreds of MB costs more than it saves -- 104 ms for 256 MB on the MI355X box,
         #  where hipMemcpy into pageable memory runs at ~50 GB/s anyway; pass out= to reuse a buffer)
         u = out if out is not None else np.empty((B, 2) + tuple(self.shape), self.rdtype)
@@ -1361,6 +1395,78 @@ class Plan:
             for buf in d_img + d_u:
                 buf.free()
         return u, iters
+
+    def _extract_stack_outputs(self, images, kvecs, klists, sigma, mask_border, kmax, chunk, out, extras, grad_mode):
+        """extract_displacement_field_stack with optional outputs: the same upload / compute / download pipeline on two sets of
+        device buffers, every output of a chunk downloaded by the download thread.  extras: name -> (asked, buffer, shape, dtype)"""
+        from concurrent.futures import ThreadPoolExecutor
+        B = images.shape[0]
+        npx = int(self.shape[0]) * int(self.shape[1])
+        item = np.dtype(self.rdtype).itemsize
+        shapes = {'u': ((2,) + tuple(self.shape), np.dtype(self.rdtype))}
+        host = {'u': out}
+        for k, (_, buf, sh, dt) in extras.items():
+            shapes[k] = (sh, np.dtype(dt))
+            host[k] = buf
+        for k, (sh, dt) in shapes.items():
+            if host[k] is None:
+                host[k] = np.empty((B,) + sh, dt)
+            elif host[k].shape != (B,) + sh or host[k].dtype != dt or not host[k].flags.c_contiguous:
+                raise ValueError('out%s must be a C-contiguous %s array of dtype %s' % ('' if k == 'u' else '_' + k, (B,) + sh, dt))
+        frame_bytes = {k: int(np.prod(sh)) * dt.itemsize for k, (sh, dt) in shapes.items()}
+        if chunk is None:   # today's budget: 16 Mpixel of u per chunk
+            chunk = max(1, min(B, (16 << 20) * 2 * item // sum(frame_bytes.values())))
+        chunk = int(max(1, min(chunk, B, 4096)))
+        nchunks = -(-B // chunk)
+        iters = np.zeros((B, 2), dtype=np.int64)
+        nbuf = min(2, nchunks)
+        d_img = [DeviceBuffer(chunk * npx * item, self.device) for _ in range(nbuf)]
+        d_out = [{k: DeviceBuffer(chunk * nb, self.device) for k, nb in frame_bytes.items()} for _ in range(nbuf)]
+        bounds = [(c * chunk, min(B, (c + 1) * chunk)) for c in range(nchunks)]
+        batched = bool(self.lib.gpa_supports_batch(self.handle))
+
+        def upload(c):
+            a, b = bounds[c]
+            d_img[c % 2].upload(np.ascontiguousarray(images[a:b], dtype=self.rdtype))
+
+        def download(c):
+            a, b = bounds[c]
+            for k, buf in d_out[c % 2].items():
+                buf.download_into(host[k][a:b])
+
+        def ptrs(c, f=0):
+            d = d_out[c % 2]
+            return [d[k].ptr + f * frame_bytes[k] if k in d else None for k in ('u', 'lockins', 'kidx', 'grads', 'weights')]
+
+        try:
+            with ThreadPoolExecutor(1) as up_pool, ThreadPoolExecutor(1) as dn_pool:
+                ups = {0: up_pool.submit(upload, 0)}
+                dns = {}
+                for c in range(nchunks):
+                    ups[c].result()                       # chunk c is on the device
+                    if c - 2 in dns:
+                        dns.pop(c - 2).result()           # its output buffers have been read out
+                    a, b = bounds[c]
+                    if batched:
+                        u_p, l_p, k_p, g_p, w_p = ptrs(c)
+                        self.extract_displacement_field_grad_batch_dev(d_img[c % 2].ptr, b - a, kvecs, klists, sigma, mask_border, kmax,
+                                                                       u_p, l_p, k_p, g_p, w_p, grad_mode, want_iters=False)
+                    else:   # shapes without a batched unwrap: the same frames one call each
+                        for f in range(b - a):
+                            u_p, l_p, k_p, g_p, w_p = ptrs(c, f)
+                            iters[a + f] = self.extract_displacement_field_dev(d_img[c % 2].ptr + f * npx * item, kvecs, klists, sigma,
+                                                                               mask_border, kmax, u_p, l_p, k_p, g_p, w_p, grad_mode)
+                    if c + 1 < nchunks:
+                        ups[c + 1] = up_pool.submit(upload, c + 1)
+                    if batched:
+                        iters[a:b] = self._batch_iters(b - a)   # synchronises: chunk c is finished
+                    dns[c] = dn_pool.submit(download, c)
+                for f in dns.values():
+                    f.result()
+        finally:
+            for buf in d_img + [b for d in d_out for b in d.values()]:
+                buf.free()
+        return (host['u'], iters) + tuple(host.get(k) for k in ('lockins', 'kidx', 'grads', 'weights'))
 
     def _batch_iters(self, nimages):
         it = (C.c_int * (2 * int(nimages)))()
@@ -1698,6 +1804,62 @@ def phases_jacobian_dev(kvecs, phases_ptr, weights_ptr, shape, nmperpixel, J_ptr
                                          h, int(bool(add_identity)), None if J_ptr is None else _ptr(int(J_ptr)),
                                          None if props_ptr is None else _ptr(int(props_ptr)), float(refangle), float(refscale),
                                          int(bool(diff)), _stream(stream)), 'gpa_phases_jacobian_dev')
+
+
+def _gradients_args(kvecs, dks, grads_shape, weights_shape):
+    """(kvecs, dks or None, lead, (nimg, n0, n1)) of grads (P, N, M, 2) or a stack (B, P, N, M, 2) with weights to match"""
+    kvecs = _f64(kvecs)
+    if kvecs.ndim != 2 or kvecs.shape[1] != 2 or not 2 <= len(kvecs) <= 8:
+        raise ValueError('kvecs must have shape (P, 2) with 2 <= P <= 8, not %s' % (kvecs.shape,))
+    if not np.isfinite(kvecs).all():
+        raise ValueError('kvecs must be finite')
+    if dks is not None:
+        dks = _f64(dks)
+        if dks.shape != kvecs.shape or not np.isfinite(dks).all():
+            raise ValueError('dks must be finite and have the shape of kvecs %s, not %s' % (kvecs.shape, dks.shape))
+    gs = tuple(int(v) for v in grads_shape)
+    if len(gs) not in (4, 5) or gs[-1] != 2 or gs[-4] != len(kvecs) or min(gs) < 1:
+        raise ValueError('grads must have shape (P, N, M, 2) or (B, P, N, M, 2) with one plane per k-vector, not %s' % (gs,))
+    if tuple(int(v) for v in weights_shape) != gs[:-1]:
+        raise ValueError('weights %s must have the shape of grads %s without its last axis' % (tuple(weights_shape), gs))
+    lead = gs[:-4]
+    return kvecs, dks, lead, (lead[0] if lead else 1, gs[-3], gs[-2])
+
+
+def gradients_jacobian(kvecs, grads, weights, nmperpixel, dks=None, add_identity=False, want_J=True, want_props=False, refangle=0.,
+                       refscale=1., diff=False, dtype=np.float64, device=0):
+    """Plan-free gpa_gradients_jacobian: phase gradients (P, N, M, 2) and weights (P, N, M) of one frame, or (B, P, N, M, 2) and
+    (B, P, N, M) of a stack, kvecs (P, 2), dks None or (P, 2) (iso_ref) -> (J (..., N, M, 2, 2) or None, props (..., 4, N, M) or
+    None): the J of Plan.phasegradient2J per frame, the props of props_from_jac(J, add_identity=True)."""
+    dtype, code = _real_dtype(dtype)
+    h = _spacing(nmperpixel)
+    kvecs, dks, lead, (nimg, n0, n1) = _gradients_args(kvecs, dks, np.shape(grads), np.shape(weights))
+    if not (want_J or want_props):
+        raise ValueError('nothing to compute: neither J nor props is wanted')
+    grads = np.ascontiguousarray(grads, dtype=dtype)
+    weights = np.ascontiguousarray(weights, dtype=dtype)
+    J = np.empty(lead + (n0, n1, 2, 2), dtype=dtype) if want_J else None
+    props = np.empty(lead + (4, n0, n1), dtype=dtype) if want_props else None
+    check(load().gpa_gradients_jacobian(int(device), code, nimg, n0, n1, len(kvecs), _ptr(kvecs), _ptr(dks), _ptr(grads),
+                                        _ptr(weights), h, int(bool(add_identity)), _ptr(J), _ptr(props), float(refangle),
+                                        float(refscale), int(bool(diff))), 'gpa_gradients_jacobian')
+    return J, props
+
+
+def gradients_jacobian_dev(kvecs, grads_ptr, weights_ptr, shape, nmperpixel, J_ptr=None, props_ptr=None, dks=None,
+                           add_identity=False, refangle=0., refscale=1., diff=False, dtype=np.float64, device=0, stream=None):
+    """gpa_gradients_jacobian_dev on device pointers: grads of `shape` (P, N, M, 2) or (B, P, N, M, 2), weights of that shape
+    without its last axis; J and props as gradients_jacobian lays them out, at least one of them; asynchronous on `stream`."""
+    dtype, code = _real_dtype(dtype)
+    h = _spacing(nmperpixel)
+    kvecs, dks, _, (nimg, n0, n1) = _gradients_args(kvecs, dks, shape, tuple(shape)[:-1])
+    if J_ptr is None and props_ptr is None:
+        raise ValueError('nothing to compute: J_ptr and props_ptr are both None')
+    check(load().gpa_gradients_jacobian_dev(int(device), code, nimg, n0, n1, len(kvecs), _ptr(kvecs), _ptr(dks),
+                                            _ptr(int(grads_ptr)), _ptr(int(weights_ptr)), h, int(bool(add_identity)),
+                                            None if J_ptr is None else _ptr(int(J_ptr)),
+                                            None if props_ptr is None else _ptr(int(props_ptr)), float(refangle), float(refscale),
+                                            int(bool(diff)), _stream(stream)), 'gpa_gradients_jacobian_dev')
 
 
 def phys_props_from_jac(jac, add_identity=False, refangle=0., refscale=1., diff=False, poisson_ratio=0.16, dtype=np.float64,

@@ -72,7 +72,7 @@ static int extract_launch(gpa_plan* p, const void* image, int P, int K, int Bx, 
   if (o.grads) {
     int32_t* kidx = o.kidx ? o.kidx : p->d_kidx;   // (the stencil reads the winners' indices)
     bool shared = false;
-    TRY(passB_phases(p, P, K, lk, kidx, p->d_sf.ptr, &shared));
+    TRY(passB_phases(p, {p->Tbuf.ptr, 1, 0}, P, K, lk, kidx, p->d_sf.ptr, &shared));
     HIP_TRY(launch_phasegrad(p->dtype, p->d_sf.ptr, K, kidx, p->n0, p->n1, p->d_kl, p->d_kr, o.grad_mode, o.grads, p->stream,
                              shared ? p->d_ystep : nullptr, P));
   } else {
@@ -311,33 +311,55 @@ static int read_batch_iters(gpa_plan* p, int B, int* iters_out) {
 // dependent launches, not by their work.
 // images: B x n0 x n1, u: B x 2 x n0 x n1 (device pointers), iters_out: 2 B counts (host, may be NULL: no
 // synchronisation then).  The results are those of B separate gpa_extract_displacement_field_dev calls, bit for bit.
-int gpa_extract_displacement_field_batch_dev(gpa_plan* p, const void* images, int B, const double* kvecs, int P,
-                                             const double* klists, int K, double sigma, int mask_border, int kmax,
-                                             void* u, int* iters_out) {
-  const char* fn = "gpa_extract_displacement_field_batch";
+// o: the optional outputs of gpa_extract_displacement_field_grad_dev with a leading image axis; all NULL: the plain stack
+// driver's launches and nothing else.  o.grads / o.absw != NULL is the one-sweep form of extract_launch, a chunk at a time.
+static int extract_batch(gpa_plan* p, const char* fn, const void* images, int B, const double* kvecs, int P,
+                         const double* klists, int K, double sigma, int mask_border, int kmax, void* u, const ExtractOut& o,
+                         int* iters_out) {
   if (!p || !images || !kvecs || !klists || !u) return fail(GPA_ERR_ARG, std::string(fn) + ": null argument");
   if (B < 1 || B > 4096) return fail(GPA_ERR_ARG, std::string(fn) + ": need 1 <= images <= 4096");
   TRY(check_ranges(p, fn, P, K, kmax));
+  if (o.grads && (o.grad_mode < 0 || o.grad_mode > 2)) return fail(GPA_ERR_ARG, std::string(fn) + ": grad_mode must be 0, 1 or 2");
   HIP_TRY(hipSetDevice(p->device));
   int Bx = 0;
-  TRY(extract_stage(p, kvecs, P, klists, K, sigma, &Bx, SWEEP_PASSB_SELECT));
+  TRY(extract_stage(p, kvecs, P, klists, K, sigma, &Bx, o.grads ? SWEEP_PASSB_PHASES : SWEEP_PASSB_SELECT));
   TRY(ensure_batch_unwrap(p, B));
   const size_t npx = (size_t)p->n0 * p->n1;
   // the sweep and the least squares of a chunk of images are ONE set of launches too (blockIdx.z / .y = image);
-  // the chunk is what fits ~3 GB of x-planes (512^2: the whole stack, 4096^2: one image at a time)
-  const size_t t_img = (size_t)Bx * npx * p->csz, l_img = (size_t)P * npx * p->csz;
-  const int chunk = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, ((size_t)3 << 30) / t_img));
-  TRY(ensure_batch_sweep(p, chunk, t_img, l_img));
+  // the chunk is what fits ~3 GB of x-planes (512^2: the whole stack, 4096^2: one image at a time) and, with gradients, ~3 GB
+  // of candidate phases (P K reals per pixel) as well
+  const size_t t_img = (size_t)Bx * npx * p->csz, l_img = (size_t)P * npx * p->csz, s_img = (size_t)P * K * npx * p->rsz;
+  const size_t k_img = (size_t)P * npx * sizeof(int32_t);
+  size_t fit = ((size_t)3 << 30) / t_img;
+  if (o.grads) fit = std::min(fit, ((size_t)3 << 30) / s_img);
+  const int chunk = (int)std::min<size_t>((size_t)B, std::max<size_t>(1, fit));
+  TRY(ensure_batch_sweep(p, chunk, t_img, o.lockins ? 0 : l_img));
+  if (o.grads) TRY(ensure_sf(p, (size_t)chunk * s_img));
+  if (o.grads && !o.kidx) TRY(plan_reserve(p, p->bK, (size_t)chunk * k_img, "batched sweep buffers"));   // (the stencil reads the winners' indices)
   int nparts = 0;
   const size_t rstride = 2 * npx;                                                     // residual slices per image
   const size_t pstride = (size_t)(unwrap_partials_buffer(&p->uwb, 2) - unwrap_partials_buffer(&p->uwb, 0));
   for (int c0 = 0; c0 < B; c0 += chunk) {
     const int nimg = std::min(chunk, B - c0);
     const void* image = (const char*)images + (size_t)c0 * npx * p->rsz;
+    // this chunk's slices of the outputs that were asked for; lock-ins nobody asked for stay in the chunk's own buffer
+    void* lk = o.lockins ? (char*)o.lockins + (size_t)c0 * l_img : p->bL.ptr;
+    int32_t* kidx = o.kidx ? o.kidx + (size_t)c0 * P * npx : nullptr;
     HIP_TRY(launch_mean(p->dtype, image, npx, p->bScratch.as<double>(), p->bMean.ptr, p->stream, nimg));
     TRY(run_passA(p, image, p->bMean.ptr, p->bT.ptr, Bx, nimg));
-    TRY(passB_select(p, {p->bT.ptr, nimg, Bx}, P, K, p->bL.ptr, nullptr, true));   // (the stack's lock-ins are never handed out)
-    HIP_TRY(launch_reconstruct_setup(p->dtype, p->bL.ptr, p->d_kmat, P, p->n0, p->n1, mask_border,
+    if (o.grads) {
+      if (!kidx) kidx = p->bK.as<int32_t>();
+      bool shared = false;
+      TRY(passB_phases(p, {p->bT.ptr, nimg, Bx}, P, K, lk, kidx, p->d_sf.ptr, &shared));
+      HIP_TRY(launch_phasegrad(p->dtype, p->d_sf.ptr, K, kidx, p->n0, p->n1, p->d_kl, p->d_kr, o.grad_mode,
+                               (char*)o.grads + (size_t)c0 * 2 * P * npx * p->rsz, p->stream, shared ? p->d_ystep : nullptr, P, nimg));
+    } else {
+      // (lock-ins nobody reads but reconstruct_setup may stay raw)
+      TRY(passB_select(p, {p->bT.ptr, nimg, Bx}, P, K, lk, kidx, !o.lockins && !o.absw));
+    }
+    if (o.absw)
+      HIP_TRY(launch_cabs(p->dtype, lk, (size_t)nimg * P * npx, (char*)o.absw + (size_t)c0 * P * npx * p->rsz, p->stream));
+    HIP_TRY(launch_reconstruct_setup(p->dtype, lk, p->d_kmat, P, p->n0, p->n1, mask_border,
                                      p->d_wnorm_b.as<char>() + (size_t)c0 * npx * p->rsz,
                                      unwrap_residual_buffer(&p->uwb, 2 * c0), unwrap_residual_buffer(&p->uwb, 2 * c0 + 1),
                                      unwrap_partials_buffer(&p->uwb, 2 * c0), unwrap_partials_buffer(&p->uwb, 2 * c0 + 1),
@@ -348,6 +370,23 @@ int gpa_extract_displacement_field_batch_dev(gpa_plan* p, const void* images, in
   p->uwb_bytes = p->uwb_base_bytes + unwrap_ring_bytes(&p->uwb);   // (the solve allocates the search directions it keeps)
   if (e != hipSuccess) return fail(GPA_ERR_HIP, std::string("batched unwrap: ") + hipGetErrorString(e));
   return iters_out ? read_batch_iters(p, B, iters_out) : GPA_OK;
+}
+
+int gpa_extract_displacement_field_batch_dev(gpa_plan* p, const void* images, int B, const double* kvecs, int P,
+                                             const double* klists, int K, double sigma, int mask_border, int kmax,
+                                             void* u, int* iters_out) {
+  return extract_batch(p, "gpa_extract_displacement_field_batch", images, B, kvecs, P, klists, K, sigma, mask_border, kmax, u,
+                       {nullptr, nullptr, nullptr, nullptr, 0}, iters_out);
+}
+
+int gpa_extract_displacement_field_grad_batch_dev(gpa_plan* p, const void* images, int B, const double* kvecs, int P,
+                                                  const double* klists, int K, double sigma, int mask_border, int kmax,
+                                                  int grad_mode, void* u, void* lockins, int32_t* kidx, void* grads, void* absw,
+                                                  int* iters_out) {
+  // (without an optional output the messages are the plain stack driver's, like everything else about the call)
+  const bool plain = !lockins && !kidx && !grads && !absw;
+  return extract_batch(p, plain ? "gpa_extract_displacement_field_batch" : "gpa_extract_displacement_field_grad_batch", images, B,
+                       kvecs, P, klists, K, sigma, mask_border, kmax, u, {lockins, kidx, grads, absw, grad_mode}, iters_out);
 }
 
 // whether gpa_extract_displacement_field_batch_dev can take this plan's image shape (the fused iteration covers it);

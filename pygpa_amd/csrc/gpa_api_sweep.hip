@@ -124,10 +124,10 @@ int passB_select(gpa_plan* p, const XPlanes& xp, int P, int K, void* lockin, int
 }
 
 // pass B of the one-sweep driver: selection for all P peaks of the staged list AND -angle of every candidate's lock-in into
-// psi [P][K][n0][n1] reals, on the x-planes pass A left in Tbuf.  The shared-forward kernel where it takes the rows and the
-// list (*shared = true: its phases lack exp(i ystep_p y), see launch_phasegrad), else the per-candidate kernel in its phases
+// psi [nimg][P][K][n0][n1] reals, on the x-planes xp pass A left (as in passB_select; lockin and kidx: nimg x P planes).
+// The shared-forward kernel where it takes the rows and the list (*shared = true: its phases lack exp(i ystep_p y), see launch_phasegrad), else the per-candidate kernel in its phases
 // mode.  The lock-ins are compensated either way.
-int passB_phases(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, void* psi, bool* shared) {
+int passB_phases(gpa_plan* p, const XPlanes& xp, int P, int K, void* lockin, int32_t* kidx, void* psi, bool* shared) {
   p->lk_raw = false;
   *shared = false;
   const bool ys = p->ys_use;   // (shared_prepare clears it: the planes pass A left are what they are)
@@ -136,8 +136,8 @@ int passB_phases(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, void* p
     p->ys_use = ys;
     if (p->sh_use && p->sh_one_kref) {
       const PassBYspec yb = {p->ys.strips, p->d_shifts};
-      const hipError_t e = launch_passB_shared_phases(p->dtype, p->ax1s, p->n0, p->Tbuf.ptr, p->ax1s.L == p->ax1.L ? p->tw1 : p->tw1s,
-                                                      p->tb, p->sh, p->sh_E, p->sh_Epad, P, K, lockin, kidx, psi, p->stream, 0,
+      const hipError_t e = launch_passB_shared_phases(p->dtype, p->ax1s, p->n0, xp.T, p->ax1s.L == p->ax1.L ? p->tw1 : p->tw1s,
+                                                      p->tb, p->sh, p->sh_E, p->sh_Epad, P, K, lockin, kidx, psi, p->stream, xp.nimg, xp.stride,
                                                       p->sh_nbl, ys ? &yb : nullptr);
       if (e == hipSuccess) {
         *shared = true;
@@ -148,7 +148,8 @@ int passB_phases(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, void* p
   }
   // (the per-candidate kernel reads spatial x-planes)
   if (ys) return fail(GPA_ERR_STATE, "pass B (phases): the staged sweep took the y-spectral pass A");
-  HIP_TRY(launch_passB_ext(p->dtype, p->ax1, p->n0, p->Tbuf.ptr, p->Hy, p->tw1, p->tb, K, 3, lockin, kidx, nullptr, psi, p->stream, P));
+  HIP_TRY(launch_passB_ext(p->dtype, p->ax1, p->n0, xp.T, p->Hy, p->tw1, p->tb, K, 3, lockin, kidx, nullptr, psi, p->stream, P, xp.nimg,
+                           xp.stride));
   return GPA_OK;
 }
 
@@ -223,7 +224,7 @@ int gpa_sweep_grad_dev(gpa_plan* p, const void* image, const double* kref, const
   // forward transform per x-plane row instead of one per candidate, the phases written by that kernel (round 6; NO_SHARED or
   // NO_SHARED_PHASES keep the per-candidate kernel: the same gradient up to rounding, tests/test_gpu_shared_passb.py)
   bool shared = false;
-  TRY(passB_phases(p, 1, K, lockin, ki, p->d_sf.ptr, &shared));
+  TRY(passB_phases(p, {p->Tbuf.ptr, 1, 0}, 1, K, lockin, ki, p->d_sf.ptr, &shared));
   HIP_TRY(launch_phasegrad(p->dtype, p->d_sf.ptr, K, ki, p->n0, p->n1, p->d_kl, p->d_kr, grad_mode, grad, p->stream,
                            shared ? p->d_ystep : nullptr));
   if (top && p->profiling) { HIP_TRY(hipStreamSynchronize(p->stream)); collect_kernel_profile(p); }

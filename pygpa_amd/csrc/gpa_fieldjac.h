@@ -71,6 +71,12 @@ GPA_FJ_HD size_t plane_offset(const Geom& g, int img, int planes, int plane) {
 }
 GPA_FJ_HD size_t pixel_offset(const Geom& g, int r, int c) { return (size_t)r * (size_t)g.n1 + (size_t)c; }
 
+// The pointwise member of the family (gradients -> J, gradients_jacobian_kernel) has no stencil, so a frame is ONE row of
+// n0 * n1 pixels to it: the same tiles, lanes and offsets, one row band per frame, a wave on 64 vectors of consecutive pixels.
+// The row length is an int: frames of up to 2^31 - 1 pixels.
+GPA_FJ_HD bool gradients_fits(int n0, int n1) { return (uint64_t)n0 * (uint64_t)n1 <= 0x7fffffffull; }
+GPA_FJ_HD Geom gradients_geom(int nimg, int n0, int n1, int elem_size) { return make_geom(nimg, 1, n0 * n1, elem_size); }
+
 // The samples a difference at index i of an axis of n >= 2 points reads: i - 1 and i + 1 inside, the sample itself in place of
 // the missing neighbour at the two ends (np.gradient's first-order edges).  hi - lo is 2 inside and 1 at an end.
 GPA_FJ_HD void stencil(int i, int n, int& lo, int& hi) {

@@ -8,6 +8,8 @@
 // Rows whose length is not a multiple of the vector (or unaligned bases) take the same path with element-wise accesses.
 // The properties come from lattice_props of gpa_jacmath.h on the J that is stored (before add_identity), the function and the
 // bits of props_kernel.
+// The third source, phase gradients and weights of a stack (phasegradient2J, :69-101, calc_props_from_phasegradient, :234-255),
+// has no stencil: gradients_jacobian_kernel is pointwise on the same geometry with a frame as one row of pixels.
 #include "gpa_internal.h"
 #include "gpa_fieldjac.h"
 #include "gpa_jacmath.h"
@@ -190,6 +192,75 @@ __global__ __launch_bounds__(FJ_LANES * FJ_WAVES) void phases_jacobian_kernel(co
   }
 }
 
+// 2 pi (kvecs + dks), P x 2, and with on != 0 the turn 2 pi dks the gradients are taken against (iso_ref of phasegradient2J)
+struct GradK { double k[16], shift[16]; int on; };
+
+// the V interleaved (d/d axis 0, d/d axis 1) pairs of the lane's pixels [c, c + V) of one peak: 2 V reals, two vectors
+template <class T, bool WIDE>
+__device__ __forceinline__ void load_pairs(const T* __restrict__ pairs, const Geom& g, int c, Vec<T> (&x)[2]) {
+  constexpr int V = FJ_VEC_BYTES / sizeof(T);
+  const T* p = pairs + 2 * pixel_offset(g, 0, c);
+  if (WIDE) {   // the pixel count is a multiple of V here, so c < n1 puts both vectors inside the frame
+    if (c < g.n1) {
+      x[0] = reinterpret_cast<const Vec<T>*>(p)[0];
+      x[1] = reinterpret_cast<const Vec<T>*>(p)[1];
+      return;
+    }
+    _Pragma("unroll") for (int k = 0; k < 2 * V; ++k) x[k / V].v[k % V] = T(0);
+  } else {
+    _Pragma("unroll") for (int k = 0; k < 2 * V; ++k) x[k / V].v[k % V] = c + k / 2 < g.n1 ? p[k] : T(0);
+  }
+}
+
+// grads: nimg x P x npx x 2, w: nimg x P x npx -> J[i, j] = (weighted least squares of grads[:, j] against gk.k)_i / nmperpixel:
+// phasegradient2J (property_extract.py:69-101), the arithmetic of jacobian_kernel (gpa_reconstruct.hip) operation for operation.
+// Pointwise: the geometry g is that of nimg frames of ONE row of npx pixels, a wave takes 64 x V consecutive pixels of a frame.
+template <class T, int P, bool WIDE>
+__global__ __launch_bounds__(FJ_LANES * FJ_WAVES) void gradients_jacobian_kernel(const T* __restrict__ grads, const T* __restrict__ w,
+                                                                                 GradK gk, Geom g, T inv_nm, T ident,
+                                                                                 Quad<T>* __restrict__ J, T* __restrict__ props,
+                                                                                 PropArgs pa) {
+  constexpr int V = FJ_VEC_BYTES / sizeof(T);
+  const int lane = threadIdx.x % FJ_LANES;
+  const uint64_t tix = (uint64_t)blockIdx.x * FJ_WAVES + threadIdx.x / FJ_LANES;
+  if (tix >= g.tiles) return;   // the whole wave
+  const Tile t = tile_of(g, tix);
+  const int c = lane_col(g, t, lane);
+  if (c >= g.n1) return;   // no cross-lane traffic here: a lane beyond the frame has nothing to do
+  const size_t npx = (size_t)g.n1;
+  const T* wf = w + plane_offset(g, t.img, P, 0);
+  const T* gf = grads + 2 * plane_offset(g, t.img, P, 0);
+  Vec<T> wv[P], gv[P][2];
+  _Pragma("unroll") for (int p = 0; p < P; ++p) {
+    wv[p] = load_vec<T, WIDE>(wf + p * npx, g, 0, c);
+    load_pairs<T, WIDE>(gf + 2 * p * npx, g, c, gv[p]);
+  }
+  Quad<T> q[V];
+  _Pragma("unroll") for (int k = 0; k < V; ++k) {
+    T wmax = T(0);
+    _Pragma("unroll") for (int p = 0; p < P; ++p) { const T a = wv[p].v[k] < T(0) ? -wv[p].v[k] : wv[p].v[k]; wmax = a > wmax ? a : wmax; }
+    const T ws = wmax > T(0) ? T(1) / wmax : T(0);
+    T a00 = 0, a01 = 0, a11 = 0, rx0 = 0, rx1 = 0, ry0 = 0, ry1 = 0;
+    _Pragma("unroll") for (int p = 0; p < P; ++p) {
+      const T k0 = (T)gk.k[2 * p], k1 = (T)gk.k[2 * p + 1], wn = wv[p].v[k] * ws, ww = wn * wn;
+      T gx = gv[p][(2 * k) / V].v[(2 * k) % V], gy = gv[p][(2 * k + 1) / V].v[(2 * k + 1) % V];
+      if (gk.on) {
+        gx = wrap_to_pi(gx - (T)gk.shift[2 * p]);
+        gy = wrap_to_pi(gy - (T)gk.shift[2 * p + 1]);
+      }
+      a00 += ww * k0 * k0; a01 += ww * k0 * k1; a11 += ww * k1 * k1;
+      rx0 += ww * k0 * gx; rx1 += ww * k1 * gx;
+      ry0 += ww * k0 * gy; ry1 += ww * k1 * gy;
+    }
+    T ux0, ux1, uy0, uy1;
+    solve2(a00, a01, a11, rx0, rx1, ux0, ux1);   // d u_i / d axis 0
+    solve2(a00, a01, a11, ry0, ry1, uy0, uy1);   // d u_i / d axis 1
+    // (rounded: what is stored with add_identity is the J of phasegradient2J plus 1, not a product fused into that sum)
+    q[k] = Quad<T>{rounded(ux0 * inv_nm), rounded(uy0 * inv_nm), rounded(ux1 * inv_nm), rounded(uy1 * inv_nm)};
+  }
+  emit<T, WIDE>(g, t, 0, c, q, ident, J, props, pa);
+}
+
 template <class T>
 __global__ __launch_bounds__(256) void phys_props_kernel(const Quad<T>* __restrict__ jac, size_t npx, T ident, T refangle,
                                                         T refscale, int diff, T delta, T* __restrict__ out) {
@@ -237,6 +308,34 @@ hipError_t launch_phases_t(int P, unsigned grid, const void* ph, const void* w, 
   return hipGetLastError();
 }
 
+template <class T, int P>
+void launch_grads_p(unsigned grid, const void* gr, const void* w, const GradK& gk, const Geom& g, double nm, bool wide,
+                    int add_identity, void* J, void* props, const PropArgs& pa, hipStream_t s) {
+  const T ident = add_identity ? T(1) : T(0), inv_nm = (T)(1.0 / nm);
+  if (wide)
+    gradients_jacobian_kernel<T, P, true><<<grid, FJ_LANES * FJ_WAVES, 0, s>>>((const T*)gr, (const T*)w, gk, g, inv_nm, ident,
+                                                                                (Quad<T>*)J, (T*)props, pa);
+  else
+    gradients_jacobian_kernel<T, P, false><<<grid, FJ_LANES * FJ_WAVES, 0, s>>>((const T*)gr, (const T*)w, gk, g, inv_nm, ident,
+                                                                                 (Quad<T>*)J, (T*)props, pa);
+}
+
+template <class T>
+hipError_t launch_grads_t(int P, unsigned grid, const void* gr, const void* w, const GradK& gk, const Geom& g, double nm, bool wide,
+                          int add_identity, void* J, void* props, const PropArgs& pa, hipStream_t s) {
+  switch (P) {
+    case 2: launch_grads_p<T, 2>(grid, gr, w, gk, g, nm, wide, add_identity, J, props, pa, s); break;
+    case 3: launch_grads_p<T, 3>(grid, gr, w, gk, g, nm, wide, add_identity, J, props, pa, s); break;
+    case 4: launch_grads_p<T, 4>(grid, gr, w, gk, g, nm, wide, add_identity, J, props, pa, s); break;
+    case 5: launch_grads_p<T, 5>(grid, gr, w, gk, g, nm, wide, add_identity, J, props, pa, s); break;
+    case 6: launch_grads_p<T, 6>(grid, gr, w, gk, g, nm, wide, add_identity, J, props, pa, s); break;
+    case 7: launch_grads_p<T, 7>(grid, gr, w, gk, g, nm, wide, add_identity, J, props, pa, s); break;
+    case 8: launch_grads_p<T, 8>(grid, gr, w, gk, g, nm, wide, add_identity, J, props, pa, s); break;
+    default: return hipErrorInvalidValue;
+  }
+  return hipGetLastError();
+}
+
 template <class T>
 void launch_field_t(unsigned grid, const void* u, const Geom& g, double h, bool wide, int add_identity, void* J, void* props,
                     const PropArgs& pa, hipStream_t s) {
@@ -276,6 +375,28 @@ hipError_t launch_phases_jacobian(int dtype, int n0, int n1, int P, const double
   if (dtype == 0)
     return launch_phases_t<float>(P, (unsigned)grid, phases, weights, km, g, nmperpixel, wide, add_identity, J, props, pa, s);
   return launch_phases_t<double>(P, (unsigned)grid, phases, weights, km, g, nmperpixel, wide, add_identity, J, props, pa, s);
+}
+
+// a frame is one row of n0 x n1 pixels to this pointwise kernel (gradients_geom of gpa_fieldjac.h)
+hipError_t launch_gradients_jacobian(int dtype, int nimg, int n0, int n1, int P, const double* kvecs, const double* dks,
+                                     const void* grads, const void* weights, double nmperpixel, int add_identity, void* J, void* props,
+                                     double refangle, double refscale, int diff, hipStream_t s) {
+  if (nimg < 1 || n0 < 1 || n1 < 1 || !gradients_fits(n0, n1) || P < 2 || P > 8 || (!J && !props)) return hipErrorInvalidValue;
+  const Geom g = gradients_geom(nimg, n0, n1, dtype == 0 ? 4 : 8);
+  const uint64_t grid = grid_blocks(g);
+  if (grid == 0) return hipErrorInvalidValue;
+  GradK gk{};
+  gk.on = dks != nullptr;
+  for (int i = 0; i < 2 * P; ++i) {   // the doubles gpa_phasegradient2J stages and passes
+    gk.k[i] = 2.0 * M_PI * (kvecs[i] + (dks ? dks[i] : 0.0));
+    gk.shift[i] = dks ? 6.283185307179586476925 * dks[i] : 0.0;
+  }
+  const bool wide = wide_ok(g, grads, weights, props);
+  const PropArgs pa{refangle, refscale, diff};
+  GPA_PROF("gradients_jacobian_kernel", s);
+  if (dtype == 0)
+    return launch_grads_t<float>(P, (unsigned)grid, grads, weights, gk, g, nmperpixel, wide, add_identity, J, props, pa, s);
+  return launch_grads_t<double>(P, (unsigned)grid, grads, weights, gk, g, nmperpixel, wide, add_identity, J, props, pa, s);
 }
 
 hipError_t launch_phys_props(int dtype, const void* jac, size_t npx, int add_identity, double refangle, double refscale, int diff,

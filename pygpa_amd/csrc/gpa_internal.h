@@ -205,10 +205,11 @@ hipError_t launch_passB(int dtype, const Axis& a1, int n0, const void* Tbuf, con
 // one peak, K candidates, the less travelled selection modes (gpa_sweep_ext.hip): mode 2 = gated selection of
 // wfr4 (gate: device K x K bytes, gate[j * K + k] != 0 where candidate k may replace the kept candidate j),
 // mode 3 = plain selection that also writes psi[k][x][y] = -angle(sf_k) of every candidate; mode 3 takes P peaks of K staged
-// candidates each in one launch (out / kidx: P planes, psi [P][K][n0][n1])
+// candidates each in one launch (out / kidx: P planes, psi [P][K][n0][n1]), and
+// nimg images (x-planes Bx planes apart, as in launch_passB; out / kidx / psi with a leading image axis)
 hipError_t launch_passB_ext(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* Hy, const void* tw1,
                             const SweepTables& tb, int K, int mode, void* out, int32_t* kidx, const uint8_t* gate,
-                            void* psi, hipStream_t s, int P = 1);
+                            void* psi, hipStream_t s, int P = 1, int nimg = 1, int Bx = 0);
 // small images (transform length <= 1024): best-of-K with the K candidates of a row split over ksplit workgroups and a
 // merge pass; part / pidx: ksplit * P * n0 * n1 complex / int32 of scratch.  Same winners and values as launch_passB.
 hipError_t launch_passB_split(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* Hy, const void* tw1,
@@ -218,9 +219,11 @@ hipError_t launch_passB_split(int dtype, const Axis& a1, int n0, const void* Tbu
 // NaN at the end, 2 the same with swapped components)
 // ystep (device, one double) != null: psi holds the phases of the shared pass B (compensated along x, lacking the phasor
 // exp(i ystep y)): no 2 pi (w - k) is added, ystep is subtracted from the differences along y
-// P peaks in one launch: psi [P][K][n0][n1], kidx [P][n0][n1], kl / kr [P K][2], ystep [P], grad [P][n0][n1][2]
+// P peaks in one launch: psi [P][K][n0][n1], kidx [P][n0][n1], kl / kr [P K][2], ystep [P], grad [P][n0][n1][2]; nimg images:
+// psi, kidx and grad with a leading image axis, the tables shared
 hipError_t launch_phasegrad(int dtype, const void* psi, int K, const int32_t* kidx, int n0, int n1, const double* kl,
-                            const double* kr, int mode, void* grad, hipStream_t s, const double* ystep = nullptr, int P = 1);
+                            const double* kr, int mode, void* grad, hipStream_t s, const double* ystep = nullptr, int P = 1,
+                            int nimg = 1);
 int passA_cols(int dtype, int lg);
 // frequency bin held by (thread, register) after the forward transform of length 2^lg
 int spec_index_rt(int lg, int tid, int reg, int elems = 16);   // elems: elements per thread of the transform (16 or 8)
@@ -274,6 +277,11 @@ hipError_t launch_field_jacobian(int dtype, int nimg, int n0, int n1, const void
 hipError_t launch_phases_jacobian(int dtype, int n0, int n1, int P, const double* kvecs, const void* phases, const void* weights,
                                   double nmperpixel, int add_identity, void* J, void* props, double refangle, double refscale,
                                   int diff, hipStream_t s);
+// phase gradients (nimg x P x n0 x n1 x 2) and weights (nimg x P x n0 x n1) of a stack -> the J of launch_jacobian, bit for bit,
+// and the props launch_props(add_identity = 1) gives for it; kvecs, dks (nullable: iso_ref) host P x 2
+hipError_t launch_gradients_jacobian(int dtype, int nimg, int n0, int n1, int P, const double* kvecs, const double* dks,
+                                     const void* grads, const void* weights, double nmperpixel, int add_identity, void* J, void* props,
+                                     double refangle, double refscale, int diff, hipStream_t s);
 hipError_t launch_phys_props(int dtype, const void* jac, size_t npx, int add_identity, double refangle, double refscale, int diff,
                              double poisson_ratio, void* out, hipStream_t s);
 

@@ -837,24 +837,24 @@ int passB_shared_nbl(int dtype, int need) {
 }
 
 // the a4 form: the same sweep, and -angle of every candidate's lock-in (without the candidate-independent phasor along y) into
-// psi_out [P][K (list positions)][n0][n1] reals.  Instantiated for the row classes the pipeline uses (2048 / 4096 / f32 8192).
+// psi_out [nimg][P][K (list positions)][n0][n1] reals (a stack: image img reads its own Bx x-planes, as in launch_passB_shared).  Instantiated for the row classes the pipeline uses (2048 / 4096 / f32 8192).
 hipError_t launch_passB_shared_phases(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* tw1, const SweepTables& tb,
                                       const PassBSharedTables& st, int E, int Epad, int P, int K, void* out, int32_t* kidx,
-                                      void* psi_out, hipStream_t s, int Bx, int nbl, const PassBYspec* ys) {
+                                      void* psi_out, hipStream_t s, int nimg, int Bx, int nbl, const PassBYspec* ys) {
   if (!psi_out || !kidx) return hipErrorInvalidValue;
   if (ys) {
     // the y-spectral form: periodic rows of 2048 / 4096 points with a rotated band
     if (a1.padded) return hipErrorInvalidValue;
 #define CASE_Y(T, LG, NBL) \
     if (a1.lg == LG && nbl == NBL && dtype == (sizeof(T) == 4 ? 0 : 1)) \
-      return run_passB_shared<T, LG, false, 16, NBL, true, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, 1, Bx, false, psi_out, ys);
+      return run_passB_shared<T, LG, false, 16, NBL, true, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, false, psi_out, ys);
     CASE_Y(float, 11, 6) CASE_Y(float, 12, 6) CASE_Y(float, 11, 8) CASE_Y(float, 12, 8) CASE_Y(double, 11, 8) CASE_Y(double, 12, 8)
 #undef CASE_Y
     return hipErrorInvalidValue;
   }
 #define CALL_P(T, LG, NBL) \
-  (a1.padded ? run_passB_shared<T, LG, true, 16, NBL, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, 1, Bx, false, psi_out) \
-             : run_passB_shared<T, LG, false, 16, NBL, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, 1, Bx, false, psi_out))
+  (a1.padded ? run_passB_shared<T, LG, true, 16, NBL, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, false, psi_out) \
+             : run_passB_shared<T, LG, false, 16, NBL, true>(a1, n0, Tbuf, tw1, tb, st, E, Epad, P, K, out, kidx, s, nimg, Bx, false, psi_out))
 #define CASE_P(LG, NBL) \
   if (a1.lg == LG && nbl == NBL) return dtype == 0 ? CALL_P(float, LG, NBL) : CALL_P(double, LG, NBL);
 #define CASE_PF32(LG, NBL) \

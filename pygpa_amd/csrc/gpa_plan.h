@@ -211,8 +211,9 @@ struct gpa_plan {
   int uwb_last_nb = 0;            // problems of the last gpa_unwrap_batch[_dev] call (gpa_unwrap_batch_finish)
   DevBuf d_wnorm_b{&ws_bytes};    // images x n0 x n1
   DevBuf h_iters_b{nullptr, true};   // pinned: 4 ints per problem
-  // sweep of a chunk of images in one set of launches: x-planes, lock-ins, means, mean scratch (doubles) per image
-  DevBuf bT{&ws_bytes}, bL{&ws_bytes}, bMean{&ws_bytes}, bScratch{&ws_bytes};
+  // sweep of a chunk of images in one set of launches: x-planes, lock-ins, means, mean scratch (doubles) per image, and the
+  // winners' indices where a stack call wants gradients but not the indices
+  DevBuf bT{&ws_bytes}, bL{&ws_bytes}, bMean{&ws_bytes}, bScratch{&ws_bytes}, bK{&ws_bytes};
   UnwrapWorkspace uw2{};          // second workspace + stream: the two components of u unwrap concurrently
   hipStream_t stream2 = nullptr;
   hipEvent_t ev_fork = nullptr, ev_join = nullptr;
@@ -315,7 +316,7 @@ int stage_sweep(gpa_plan* p, const double* krefs, int P, const double* klists, i
 int ensure_yspec(gpa_plan* p, int nimg, int Bx);
 int run_passA(gpa_plan* p, const void* image, const void* mean, void* Tbuf, int Bx, int nimg);
 int passB_select(gpa_plan* p, const XPlanes& xp, int P, int K, void* lockin, int32_t* kidx, bool raw);
-int passB_phases(gpa_plan* p, int P, int K, void* lockin, int32_t* kidx, void* psi, bool* shared);
+int passB_phases(gpa_plan* p, const XPlanes& xp, int P, int K, void* lockin, int32_t* kidx, void* psi, bool* shared);
 void collect_kernel_profile(gpa_plan* p);
 // the tail of a profiled entry point: drain the stream, read the kernel events of the call
 inline int prof_finish(gpa_plan* p) {

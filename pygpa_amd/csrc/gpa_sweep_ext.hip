@@ -18,14 +18,16 @@ namespace gpa {
 // then + 2 pi (w - kref) of the matching axis and wrapToPi(2 g) / 2 (:807-812).  wfr2_grad differentiates the
 // phase of the COMPENSATED lock-in and wraps per candidate; that is the same number modulo pi, i.e. the same
 // result up to rounding (tests/test_oracle_golden.py::test_variants_gradient_spellings).
-// The peak comes from the grid (blockIdx.z): psi [P][K][n0][n1], kidx [P][n0][n1], kl / kr at p K + k, ystep[p], grad
-// [P][n0][n1][2] -- one launch for the P peaks of the fused driver; a single sweep is the launch with gridDim.z = 1.
+// Image and peak come from the grid (blockIdx.z = image * P + peak): psi [nimg][P][K][n0][n1], kidx [nimg][P][n0][n1], grad
+// [nimg][P][n0][n1][2]; the tables are those of the peak, the same for every image: kl / kr at peak K + k, ystep[peak] -- one
+// launch for the P peaks of the fused driver (of every image of a chunk, in the stack driver); a single sweep is the launch
+// with gridDim.z = 1.
 template <class T>
 __global__ __launch_bounds__(256) void phasegrad_kernel(const T* __restrict__ psi, int K, const int32_t* __restrict__ kidx,
                                                        int n0, int n1, const double* __restrict__ kl,
                                                        const double* __restrict__ kr, int mode, T* __restrict__ grad,
-                                                       const double* __restrict__ ystep) {
-  const int y = blockIdx.x * 256 + threadIdx.x, x = blockIdx.y, p = blockIdx.z;
+                                                       const double* __restrict__ ystep, int P) {
+  const int y = blockIdx.x * 256 + threadIdx.x, x = blockIdx.y, p = blockIdx.z, pt = p % P;
   if (y >= n1) return;
   const size_t npx = (size_t)n0 * n1, o = (size_t)x * n1 + y;
   kidx += (size_t)p * npx;
@@ -49,9 +51,9 @@ __global__ __launch_bounds__(256) void phasegrad_kernel(const T* __restrict__ ps
     if (ystep) {
       // compensated form (the shared pass B's phases): psi is -angle of the lock-in compensated along x and lacking only the
       // candidate-independent phasor exp(i ystep y): the compensated phase differs by -ystep per column, and 2 pi (w - k) is in it
-      g1 = (T)((double)g1 - ystep[p]);
+      g1 = (T)((double)g1 - ystep[pt]);
     } else {
-      const size_t b = (size_t)p * K + bi;
+      const size_t b = (size_t)pt * K + bi;
       g0 += (T)(6.28318530717958647692 * (kl[2 * b] - kr[2 * b]));
       g1 += (T)(6.28318530717958647692 * (kl[2 * b + 1] - kr[2 * b + 1]));
     }
@@ -65,13 +67,14 @@ __global__ __launch_bounds__(256) void phasegrad_kernel(const T* __restrict__ ps
 }
 
 hipError_t launch_phasegrad(int dtype, const void* psi, int K, const int32_t* kidx, int n0, int n1, const double* kl,
-                            const double* kr, int mode, void* grad, hipStream_t s, const double* ystep, int P) {
-  dim3 grid((n1 + 255) / 256, n0, P);
+                            const double* kr, int mode, void* grad, hipStream_t s, const double* ystep, int P, int nimg) {
+  if (P < 1 || nimg < 1 || (size_t)P * nimg > 65535) return hipErrorInvalidValue;
+  dim3 grid((n1 + 255) / 256, n0, P * nimg);
   GPA_PROF("phasegrad_kernel", s);
   if (dtype == 0)
-    phasegrad_kernel<float><<<grid, 256, 0, s>>>((const float*)psi, K, kidx, n0, n1, kl, kr, mode, (float*)grad, ystep);
+    phasegrad_kernel<float><<<grid, 256, 0, s>>>((const float*)psi, K, kidx, n0, n1, kl, kr, mode, (float*)grad, ystep, P);
   else
-    phasegrad_kernel<double><<<grid, 256, 0, s>>>((const double*)psi, K, kidx, n0, n1, kl, kr, mode, (double*)grad, ystep);
+    phasegrad_kernel<double><<<grid, 256, 0, s>>>((const double*)psi, K, kidx, n0, n1, kl, kr, mode, (double*)grad, ystep, P);
   return hipGetLastError();
 }
 
@@ -144,19 +147,20 @@ hipError_t launch_passB_split(int dtype, const Axis& a1, int n0, const void* Tbu
   return hipGetLastError();
 }
 
-// P peaks (grid.y) of K candidates; mode PB_GATED (one peak; gate: device K x K bytes) or PB_PHASES (psi: P x K x n0 x n1)
+// P peaks (grid.y) of K candidates; mode PB_GATED (one peak; gate: device K x K bytes) or PB_PHASES (psi: P x K x n0 x n1; of
+// nimg images whose x-planes lie Bx planes apart: grid.y = image * P + peak, psi nimg x P x K x n0 x n1)
 hipError_t launch_passB_ext(int dtype, const Axis& a1, int n0, const void* Tbuf, const void* Hy, const void* tw1,
                             const SweepTables& tb, int K, int mode, void* out, int32_t* kidx, const uint8_t* gate,
-                            void* psi, hipStream_t s, int P) {
+                            void* psi, hipStream_t s, int P, int nimg, int Bx) {
 #define CALL_X(T, LG, PD)                                                                                        \
   (mode == PB_GATED ? run_passB<T, LG, PD, PB_GATED>(a1, n0, Tbuf, Hy, tw1, tb, 1, K, out, kidx, gate, psi, s)   \
-                    : run_passB<T, LG, PD, PB_PHASES>(a1, n0, Tbuf, Hy, tw1, tb, P, K, out, kidx, gate, psi, s))
+                    : run_passB<T, LG, PD, PB_PHASES>(a1, n0, Tbuf, Hy, tw1, tb, P, K, out, kidx, gate, psi, s, 1, nimg, Bx))
 #define CASE_X(LG)                                                                         \
   case LG:                                                                                 \
     if (dtype == 0) return a1.padded ? CALL_X(float, LG, true) : CALL_X(float, LG, false); \
     else return a1.padded ? CALL_X(double, LG, true) : CALL_X(double, LG, false);
   if (mode != PB_GATED && mode != PB_PHASES) return hipErrorInvalidValue;
-  if (P < 1 || (mode == PB_GATED && P != 1)) return hipErrorInvalidValue;
+  if (P < 1 || nimg < 1 || (size_t)P * nimg > 65535 || (mode == PB_GATED && (P != 1 || nimg != 1))) return hipErrorInvalidValue;
   switch (a1.lg) { GPA_FOR_LG(CASE_X) }
 #undef CASE_X
 #undef CALL_X

@@ -635,16 +635,28 @@ def extract_displacement_field(image, kvecs, sigma=None, kwscale=2.5, ksteps=3, 
     return u
 
 
-def extract_displacement_field_stack(images, kvecs, sigma=None, kwscale=2.5, ksteps=3, klists=None, dtype=None):
+def extract_displacement_field_stack(images, kvecs, sigma=None, kwscale=2.5, ksteps=3, klists=None, dtype=None, return_gs=False,
+                                     wfr_func=optwfr2):
     """`extract_displacement_field` of every image of a stack (B, N, M) with one set of k-vectors -- frames of a
     movie, a tilt or temperature series -- in ONE device call: every kernel of the driver takes an image index from
     its grid, so the ~110 dependent launches that bound a small image are paid once per stack (512^2 frames: x4
     the single-image rate).  No counterpart in the reference (a Python loop over `extract_displacement_field`,
     geometric_phase_analysis.py:907-932, gives the same numbers).
-    Returns u of shape (B, 2, N, M)."""
+    Returns u of shape (B, 2, N, M).
+
+    ``wfr_func`` must be a registered native sweep (register_native_sweep: this module's optwfr2 / wfr2_grad_opt /
+    wfr2_grad_vec, cuGPA's wfr2_grad_opt / wfr2_grad_single); any other callable raises ValueError -- there is no host loop
+    here.  The plan dtype follows the registration as in the single call.  ``return_gs=True`` returns (us, gs): gs[b][p] is
+    the mapping the single call returns for frame b and peak p (the same keys in the same order), its arrays views of the
+    stacked outputs of the one sweep."""
     images = np.asarray(images)
     if images.ndim != 3:
         raise ValueError('images must be a stack (B, N, M)')
+    native = _native_sweep(wfr_func)
+    if native is None:
+        raise ValueError('extract_displacement_field_stack: wfr_func %r is not a registered native sweep '
+                         '(register_native_sweep); a stack has no per-peak host loop' % (wfr_func,))
+    keys, sweep_dtype = native
     kvecs = np.asarray(kvecs, dtype=np.float64).reshape(-1, 2)
     norms = np.linalg.norm(kvecs, axis=1)
     kw = norms.mean() / kwscale
@@ -655,8 +667,26 @@ def extract_displacement_field_stack(images, kvecs, sigma=None, kwscale=2.5, kst
     klists = [np.asarray(kl, dtype=np.float64).reshape(-1, 2) for kl in klists]
     K = max(len(kl) for kl in klists)
     padded = np.stack([np.concatenate([kl, np.repeat(kl[-1:], K - len(kl), axis=0)]) for kl in klists])
-    plan = _lib.get_plan(images.shape[1:], len(kvecs) * K, DEFAULT_DTYPE if dtype is None else dtype)
-    return plan.extract_displacement_field_stack(images, kvecs, padded, sigma, int(2 * sigma), kmax=10)[0]
+    out_dtype = DEFAULT_DTYPE if dtype is None else dtype
+    plan = _lib.get_plan(images.shape[1:], len(kvecs) * K, out_dtype if sweep_dtype is None else sweep_dtype)
+    if not return_gs:
+        us = plan.extract_displacement_field_stack(images, kvecs, padded, sigma, int(2 * sigma), kmax=10)[0]
+        return us if sweep_dtype is None else np.asarray(us, dtype=out_dtype)
+    us, _, lock, kidx, grads, _ = plan.extract_displacement_field_stack(images, kvecs, padded, sigma, int(2 * sigma), kmax=10,
+                                                                        want_lockins=True, want_kidx=True,
+                                                                        want_grads='grad' in keys)
+    gs = []
+    for b in range(len(images)):
+        frame = []
+        for p in range(len(kvecs)):
+            full = {'lockin': lock[b, p], 'kidx': kidx[b, p]}
+            if 'w' in keys:
+                full['w'] = _w_from_kidx(kidx[b, p], padded[p])
+            if grads is not None:
+                full['grad'] = grads[b, p]
+            frame.append({k: full[k] for k in keys})
+        gs.append(frame)
+    return np.asarray(us, dtype=out_dtype), gs
 
 
 def gaussian_deconvolve(data, sigma, dr=20, balance=5000, dtype=None):

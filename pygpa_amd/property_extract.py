@@ -14,6 +14,10 @@ kernel, with J, the properties of 1 + J, or both as outputs; u2J_dev and phases2
 u2Jac works (the reference's loses its spacing argument and raises TypeError); `weights` must have the shape of `phases`; shape
 errors are ValueError before the library is touched.  The moire conversions (J_2_J_diff, moire_props_*, f2angle) are not provided.
 
+phasegradient2J_stack, calc_props_from_phasegradient_stack and phasegradient2J_dev take the gradients and weights of a whole stack
+(extract_displacement_field_stack(..., return_gs=True)) through one plan-free pass (gpa_gradients_jacobian): J, the properties of
+1 + J, or both, frame b equal to the single functions bit for bit.  The single functions keep their two-kernel path.
+
 The Kerelsky decomposition of the displacement-gradient field -- Kerelsky_Jac, Kerelsky_J and its per-pixel worker
 iterate_J_leastsq (property_extract.py:696-883) -- runs in the same library (gpa_kerelsky_fit, one bounded Levenberg-Marquardt
 solve per pixel and lane, csrc/gpa_kerelsky.h) in place of scipy.optimize.least_squares behind a dask gufunc; Kerelsky_J_dev is its
@@ -95,6 +99,50 @@ def calc_props_from_phasegradient(kvecs, grads, weights, nmperpixel, dtype=None)
     J = phasegradient2J(kvecs, grads, weights, nmperpixel, dtype=dtype)
     _, theta_0, _ = get_initial_props(kvecs)
     return props_from_J(J, refangle=theta_0, dtype=dtype)
+
+
+# ---- a stack of frames: gradients -> J and properties in one pass (gpa_gradients_jacobian, no plan) ----------------------------
+def _stack_order(kvecs, grads, weights, sort, iso_ref):
+    """(kvecs in solve order, grads[:, order], dks or None) of a stack: the bookkeeping of phasegradient2J"""
+    kvecs = np.asarray(kvecs, dtype=np.float64).reshape(-1, 2)
+    grads = np.asarray(grads)
+    if grads.ndim != 5 or np.ndim(weights) != 4:
+        raise ValueError('grads must have shape (B, P, N, M, 2) and weights (B, P, N, M)')
+    if sort != 0 and iso_ref:   # (without iso_ref the single function solves in the given order, whatever `sort` says)
+        angles = np.arctan2(kvecs[:, 1], kvecs[:, 0])
+        order = np.argsort(sort * periodic_difference(angles, periodic_average(angles)))
+        kvecs, grads = kvecs[order], grads[:, order]
+    return kvecs, grads, (calc_diff_from_isotropic(kvecs) if iso_ref else None)
+
+
+def phasegradient2J_stack(kvecs, grads, weights, nmperpixel, iso_ref=True, sort=0, dtype=None):
+    """phasegradient2J of every frame of a stack in one call: grads (B, P, N, M, 2) and weights (B, P, N, M), e.g. the
+    outputs of extract_displacement_field_stack(..., return_gs=True), -> J (B, N, M, 2, 2), frame b equal to
+    phasegradient2J(kvecs, grads[b], weights[b], ...) bit for bit.  ``sort != 0`` reorders kvecs and grads[:, order] but not
+    the weights, as the single function does."""
+    lk, lg, dks = _stack_order(kvecs, grads, weights, sort, iso_ref)
+    return _lib.gradients_jacobian(lk, lg, weights, nmperpixel, dks=dks, dtype=_dt(dtype))[0]
+
+
+def calc_props_from_phasegradient_stack(kvecs, grads, weights, nmperpixel, dtype=None):
+    """calc_props_from_phasegradient of every frame of a stack in one pass: (B, 4, N, M), frame b equal to the single function's
+    bit for bit.  Only the properties are asked for, so J is never stored."""
+    lk, lg, dks = _stack_order(kvecs, grads, weights, 0, True)
+    _, theta_0, _ = get_initial_props(kvecs)
+    return _lib.gradients_jacobian(lk, lg, weights, nmperpixel, dks=dks, want_J=False, want_props=True, refangle=theta_0,
+                                   dtype=_dt(dtype))[1]
+
+
+def phasegradient2J_dev(kvecs, grads_ptr, weights_ptr, shape, nmperpixel, J_ptr=None, props_ptr=None, iso_ref=True, stream=None,
+                        add_identity=False, refangle=0., refscale=1., diff=False, dtype=None, device=0):
+    """phasegradient2J_stack for gradients that are resident on the device (e.g. the grads and weights of
+    Plan.extract_displacement_field_grad_batch_dev): grads_ptr holds `shape` = (P, N, M, 2) or (B, P, N, M, 2) values of `dtype`,
+    weights_ptr that shape without its last axis.  J_ptr receives (B,) N x M x 2 x 2 values, props_ptr (B,) 4 x N x M --
+    props_from_J of that J -- in the same pass; at least one of the two.  Asynchronous on `stream`."""
+    kvecs = np.asarray(kvecs, dtype=np.float64).reshape(-1, 2)
+    _lib.gradients_jacobian_dev(kvecs, grads_ptr, weights_ptr, shape, nmperpixel, J_ptr=J_ptr, props_ptr=props_ptr,
+                                dks=calc_diff_from_isotropic(kvecs) if iso_ref else None, add_identity=add_identity,
+                                refangle=refangle, refscale=refscale, diff=diff, dtype=_dt(dtype), device=device, stream=stream)
 
 
 # ---- J and properties from a displacement field or from phases (property_extract.py:13-52, :181-217, :258-278) ---------------
